@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BtcDet hot path on MI355X: scenes/s forward+backward, KITTI-Car configuration, bs=2 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one pass of the hot path over one synthetic batch whose raw points already sit in HBM:
@@ -19,12 +19,14 @@ occupancy bucket's all-reduce, the occupancy group's optimizer step and the NEXT
 thread launches with the occupancy weights it has just updated.  K timed steps contain K of everything; every forward pass sees the
 weights the in-order loop would give it (tests/test_hip_prefetch.py).  The same schedule runs at N = 1 and N > 1.
 BTC_SCHEDULE=in_order|split|pipelined overrides.  fp32 throughout (--features bf16: BASELINE.json configs[2]).
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, primes and warms up, times K steps, writes
+the last timed step's outputs (--dump-outputs DIR) and prints the line.  --full adds, after the timed steps,
   roofline      the dominant kernel (conv_apply = fused sparse conv fwd/dgrad) timed live with HIP events
   cpu_baseline  the CPU oracle timed on the host cores for a bounded sample of the same workload (N = 1 only)
   config.in_order_scenes_per_s   the same modules driven in order on one stream (what the reference's own loop gets)
   config.with_rpn_heads          the step with BaseBEVBackbone + AnchorHeadSingle behind the BEV map (second, shorter run).
   config.with_all_heads          ... and the ROI head (proposals, targets, ConvHead, rcnn loss) behind that: the reference's whole loss.
+  config.recurring_batches_scenes_per_s, config.predicted_scaling_eff, other_kernels, rulebook_hbm_GBps.
 """
 import argparse
 import json
@@ -226,7 +228,16 @@ def main():
                     help="standin (headline): L2 stand-ins on the two tensors the heads behind the hot path consume; rpn: BaseBEVBackbone + "
                          "AnchorHeadSingle with the reference's RPN loss (btcnet.py:108-114) behind the BEV map, the ROI head's tensor keeps "
                          "its stand-in (ConvHead is not built)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned and left in the model (its loss, every floating-point "
+                         "state_dict entry) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the secondary ones (in-order rate, recurring batches, RPN / all-heads "
+                         "runs, roofline leg, CPU baseline; --no-extras / --no-roofline / --no-cpu-baseline still drop single ones) and "
+                         "quote the committed-profile estimates; a plain run times the headline only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_roofline = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -334,8 +345,8 @@ def main():
 
     def timed_run(step_fn, n_steps, n_warm, end_stream, pool=None, rows_of=None):
         """n_warm untimed steps, then exactly n_steps timed ones bracketed by barrier + synchronize -> (seconds, per-step ms, hipMallocs,
-        per-step level rows).  pool: the batches to cycle through (default: the distinct ones, continuing where the last run stopped);
-        rows_of: a model whose last_level_rows (host integers, no read-back) are logged per timed step"""
+        per-step level rows, what the last step returned).  pool: the batches to cycle through (default: the distinct ones, continuing
+        where the last run stopped); rows_of: a model whose last_level_rows (host integers, no read-back) are logged per timed step"""
         if pool is None:
             pool, base = batches, cursor[0]
             cursor[0] += n_warm + n_steps
@@ -353,10 +364,11 @@ def main():
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_steps + 1)]
         allocs0 = torch.cuda.memory_stats(device).get("num_device_alloc", 0)
         rows = []
+        out = None
         t0 = time.perf_counter()
         marks[0].record(end_stream)
         for i in range(n_warm, n_warm + n_steps):  # each step prepares its successor: K steps, K preparations
-            call(i)
+            out = call(i)
             marks[i - n_warm + 1].record(end_stream)  # end of the step's work on the stream its last kernel runs on (no host wait)
             if rows_of is not None:
                 rows.append(getattr(rows_of, "last_level_rows", None))
@@ -364,25 +376,28 @@ def main():
         dt = time.perf_counter() - t0
         ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(n_steps)]
         ms = sorted(ms)
-        return dt, ms, torch.cuda.memory_stats(device).get("num_device_alloc", 0) - allocs0, rows
+        return dt, ms, torch.cuda.memory_stats(device).get("num_device_alloc", 0) - allocs0, rows, out
 
     # Setup, before the W warmup steps: the caching allocator, the per-batch-size geometry plans and the flat optimizer buffers reach
     # their steady state only after every one of the 4 synthetic batches has been seen a few times; a short W (the driver's choice)
     # would otherwise leave hipMalloc calls and plan construction inside the timed region (config.priming_steps in the JSON).
-    dt, per_step_ms, device_allocs, level_rows = timed_run(step, args.steps, priming + args.warmup, step.end_stream, rows_of=model)
+    dt, per_step_ms, device_allocs, level_rows, last_loss = timed_run(step, args.steps, priming + args.warmup, step.end_stream, rows_of=model)
     dt = max_over_ranks(dt, dist, device)
+    if args.dump_outputs and rank == 0:   # before anything else steps the model (--full's secondary runs train it further)
+        dump_outputs(args.dump_outputs, last_loss, model)
     if getattr(step, "timing", None) and rank == 0:   # BTC_TRAINER_TIMING=1: host milliseconds per phase and step of the timed region
         n = max(step.timing.get("n", 1), 1)
         print("trainer host ms per step:", {k: round(1e3 * v / n, 3) for k, v in step.timing.items() if k != "n"}, file=sys.stderr)
 
-    # ---- secondary measurements (outside the timed region, N = 1 reporting only; --no-extras skips them)
+    # ---- secondary measurements (--full only: outside the timed region, N = 1 reporting only; --no-extras skips them)
     extras = {}
     want_extras = not args.no_extras and not waymo
-    plain_step = make_step(model, model, model.dataset.data_processor, [opt], grad_sync, det_loss=model.det_loss)   # one stream, one thread
+    if want_extras or not args.no_roofline:
+        plain_step = make_step(model, model, model.dataset.data_processor, [opt], grad_sync, det_loss=model.det_loss)   # one stream, one thread
     if want_extras:
         # what the reference's own loop (train_one_epoch_multi_opt) gets from these modules unchanged: in order, one stream
         k_in = min(args.steps, 10)
-        dt_in, _, _, _ = timed_run(lambda b, nxt: plain_step(b), k_in, 2, None)
+        dt_in, _, _, _, _ = timed_run(lambda b, nxt: plain_step(b), k_in, 2, None)
         dt_in = max_over_ranks(dt_in, dist, device)
         extras["in_order_scenes_per_s"] = round(bs * world * k_in / dt_in, 2)
     # roofline leg: the SAME steps once more, in order, with a HIP event pair around every sparse-conv / rulebook launch
@@ -403,7 +418,7 @@ def main():
         # round 3's headline, kept for continuity: the same schedule over FOUR recurring batches, which the live optimizer memorises
         # (after ~15 steps the occupancy head predicts few occupied cells and the detection levels shrink)
         k_rec = min(args.steps, 20)
-        dt_rec, _, _, rows_rec = timed_run(step, k_rec, 16, step.end_stream, pool=batches[:4], rows_of=model)
+        dt_rec, _, _, rows_rec, _ = timed_run(step, k_rec, 16, step.end_stream, pool=batches[:4], rows_of=model)
         dt_rec = max_over_ranks(dt_rec, dist, device)
         extras["recurring_batches_scenes_per_s"] = {"scenes_per_s": round(bs * world * k_rec / dt_rec, 2), "steps": k_rec, "warm": 16,
                                                     "level_rows_last_step": rows_rec[-1] if rows_rec else None,
@@ -418,7 +433,7 @@ def main():
         # 32 untimed steps first: the vendor library's convolution searches, the allocator and the thread placement of a NEW model and trainer
         # (12 were not enough: 88.7 in this line against 164.5 for `bench.py --heads rpn` alone, same box)
         k_r = min(args.steps, 20)
-        dt_r, ms_r, _, _ = timed_run(tr_r._step, k_r, 32, tr_r._step.end_stream)
+        dt_r, ms_r, _, _, _ = timed_run(tr_r._step, k_r, 32, tr_r._step.end_stream)
         dt_r = max_over_ranks(dt_r, dist, device)
         extras["with_rpn_heads"] = {"scenes_per_s": round(bs * world * k_r / dt_r, 2), "ms_per_step": round(1e3 * dt_r / k_r, 3), "steps": k_r,
                                     "what": "BaseBEVBackbone + AnchorHeadSingle (RPN cls / loc / dir loss, targets assigned in the prepared front) "
@@ -431,7 +446,7 @@ def main():
         with _StdoutToStderr():
             tr_f = HotPathTrainer(model_f, schedule=schedule, distributed=with_reducer, det_loss=model_f.det_loss)
         k_f = min(args.steps, 20)
-        dt_f, ms_f, _, _ = timed_run(tr_f._step, k_f, 32, tr_f._step.end_stream)
+        dt_f, ms_f, _, _, _ = timed_run(tr_f._step, k_f, 32, tr_f._step.end_stream)
         dt_f = max_over_ranks(dt_f, dist, device)
         tr_f.finish()
         extras["with_all_heads"] = {"scenes_per_s": round(bs * world * k_f / dt_f, 2), "ms_per_step": round(1e3 * dt_f / k_f, 3), "steps": k_f,
@@ -483,7 +498,7 @@ def main():
                        "level_rows": level_row_stats(level_rows), "priming_steps": priming, "heads": args.heads},
         }
         result["config"].update(extras)
-        straggler = straggler_estimate()
+        straggler = straggler_estimate() if args.full else None
         if straggler is not None:
             result["config"]["predicted_scaling_eff"] = straggler
         if prof is not None:
@@ -560,6 +575,29 @@ def level_row_stats(rows):
     out["what"] = ("occ_out: rows of the occupancy decoder's output level; det_voxels: detection-grid voxels of the raw points; "
                    "det_voxels_after_pass_occ: + the voxels PassOccVox adds (M''); det_L0..L3 / det_out: the backbone's levels")
     return out
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # the .npy payloads of --dump-outputs together (headers stay far below the 64 MB bound)
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what a caller of the timed step holds after its last call -- the loss it returned (loss.npy) and the trained model
+    (state.<state_dict key>.npy for every floating-point entry: parameters after the optimizer step, BatchNorm running statistics),
+    float32.  Under the pipelined schedule the last step has also run the NEXT batch's occupancy forward in training mode (its successor's
+    head start), so the occupancy branch's running statistics include that batch; the detection branch's end with the last timed one.
+    Were they larger than DUMP_LIMIT_BYTES together, each array would be cut to the same seeded sample of its elements.
+    With the same arguments two runs write the same bits (tests/test_hip_bench_contract.py)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().cpu().numpy()}
+    for k, v in model.state_dict().items():
+        if v.is_floating_point():
+            arrays["state." + k] = v.detach().float().cpu().numpy()
+    keep = min(1.0, DUMP_LIMIT_BYTES / float(sum(a.nbytes for a in arrays.values())))
+    for name, a in arrays.items():
+        if keep < 1.0:
+            idx = np.random.default_rng(0).choice(a.size, max(1, int(a.size * keep)), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def straggler_estimate():

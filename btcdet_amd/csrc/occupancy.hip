@@ -87,14 +87,20 @@ __device__ __forceinline__ size_t cell_index(const OccParams& P, int b, int z, i
   return (((size_t)b * P.nz + z) * P.ny + y) * P.nx + x;
 }
 
-__device__ __forceinline__ void accumulate(float* __restrict__ sums, int32_t* __restrict__ cnt, const OccParams& P, int b, int z,
+// Per-cell coordinate sums in fixed point (OCC_FIX units per metre / degree, int64): integer adds commute, so a cell's sum is the same
+// whatever order its points arrive in (with float atomics res_mtrx would depend on that order).  Each value is rounded
+// to 2^-32 once; the int64 sum is exact while |value| x points of a cell < 2^31 (coordinates are metres / degrees: far below).
+#define OCC_FIX 4294967296.0
+__device__ __forceinline__ unsigned long long occ_fix(float v) { return (unsigned long long)__double2ll_rn((double)v * OCC_FIX); }
+
+__device__ __forceinline__ void accumulate(long long* __restrict__ sums, int32_t* __restrict__ cnt, const OccParams& P, int b, int z,
                                            int y, int x, float px, float py, float pz) {
   size_t vol = (size_t)P.nz * P.ny * P.nx;
   size_t sp = ((size_t)z * P.ny + y) * P.nx + x;
-  float* s = sums + (size_t)b * 3 * vol + sp;
-  atomicAdd(s, px);
-  atomicAdd(s + vol, py);
-  atomicAdd(s + 2 * vol, pz);
+  unsigned long long* s = (unsigned long long*)(sums + (size_t)b * 3 * vol + sp);
+  atomicAdd(s, occ_fix(px));
+  atomicAdd(s + vol, occ_fix(py));
+  atomicAdd(s + 2 * vol, occ_fix(pz));
   atomicAdd(cnt + (size_t)b * vol + sp, 1);
 }
 
@@ -104,8 +110,8 @@ __global__ __launch_bounds__(256) void occ_point_pass(float* __restrict__ voxels
                                                       const float* __restrict__ mirr_flag, const float* __restrict__ rot_z, OccParams P,
                                                       uint8_t* __restrict__ voxelwise, uint8_t* __restrict__ smap,
                                                       uint8_t* __restrict__ fore_mask, uint8_t* __restrict__ mirr_mask,
-                                                      float* __restrict__ fore_sum, int32_t* __restrict__ fore_cnt,
-                                                      float* __restrict__ mirr_sum, int32_t* __restrict__ mirr_cnt) {
+                                                      long long* __restrict__ fore_sum, int32_t* __restrict__ fore_cnt,
+                                                      long long* __restrict__ mirr_sum, int32_t* __restrict__ mirr_cnt) {
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)M * Pn) return;
   int v = (int)(t / Pn), slot = (int)(t % Pn);
@@ -310,7 +316,7 @@ __global__ __launch_bounds__(256) void occ_ray_project(const uint8_t* __restrict
 
 __global__ __launch_bounds__(256) void occ_bm_pass(const float* __restrict__ bm, int n, const float* __restrict__ gt,
                                                    const int32_t* __restrict__ gt_num, const float* __restrict__ rot_z, OccParams P,
-                                                   uint8_t* __restrict__ bm_mask, float* __restrict__ bm_sum,
+                                                   uint8_t* __restrict__ bm_mask, long long* __restrict__ bm_sum,
                                                    int32_t* __restrict__ bm_cnt) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -370,26 +376,26 @@ struct OccOut {
   int32_t* pos_all_num;
 };
 
-__device__ __forceinline__ void mean_res(const float* __restrict__ sums, const int32_t* __restrict__ cnt, const OccParams& P, int b,
+__device__ __forceinline__ void mean_res(const long long* __restrict__ sums, const int32_t* __restrict__ cnt, const OccParams& P, int b,
                                          size_t sp, size_t vol, float cx, float cy, float cz, float out[3]) {
   int n = cnt[(size_t)b * vol + sp];
   if (n <= 0) {
     out[0] = out[1] = out[2] = 0.f;
     return;
   }
-  const float* s = sums + (size_t)b * 3 * vol + sp;
+  const long long* s = sums + (size_t)b * 3 * vol + sp;
   float fn = (float)n;
-  out[0] = __fsub_rn(__fdiv_rn(s[0], fn), cx);
-  out[1] = __fsub_rn(__fdiv_rn(s[vol], fn), cy);
-  out[2] = __fsub_rn(__fdiv_rn(s[2 * vol], fn), cz);
+  out[0] = __fsub_rn(__fdiv_rn((float)((double)s[0] / OCC_FIX), fn), cx);
+  out[1] = __fsub_rn(__fdiv_rn((float)((double)s[vol] / OCC_FIX), fn), cy);
+  out[2] = __fsub_rn(__fdiv_rn((float)((double)s[2 * vol] / OCC_FIX), fn), cz);
 }
 
 __global__ __launch_bounds__(256) void occ_finalize(const float* __restrict__ gt, const int32_t* __restrict__ gt_num,
                                                     const float* __restrict__ rot_z, const float* __restrict__ centers /* nz,ny,nx,3 */,
                                                     OccParams P, const uint8_t* __restrict__ occ_raw, const float* __restrict__ colmin,
-                                                    const uint8_t* __restrict__ mirr_raw, const float* __restrict__ fore_sum,
-                                                    const int32_t* __restrict__ fore_cnt, const float* __restrict__ mirr_sum,
-                                                    const int32_t* __restrict__ mirr_cnt, const float* __restrict__ bm_sum,
+                                                    const uint8_t* __restrict__ mirr_raw, const long long* __restrict__ fore_sum,
+                                                    const int32_t* __restrict__ fore_cnt, const long long* __restrict__ mirr_sum,
+                                                    const int32_t* __restrict__ mirr_cnt, const long long* __restrict__ bm_sum,
                                                     const int32_t* __restrict__ bm_cnt, OccOut O) {
   const size_t vol = (size_t)P.nz * P.ny * P.nx;
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -480,7 +486,7 @@ __global__ __launch_bounds__(256) void occ_finalize(const float* __restrict__ gt
 
 }  // namespace
 
-static size_t occ_ws_layout(const BtcOccConfig* c, void* ws, uint8_t** smap, uint8_t** occ_raw, uint8_t** mirr_raw, float** sums,
+static size_t occ_ws_layout(const BtcOccConfig* c, void* ws, uint8_t** smap, uint8_t** occ_raw, uint8_t** mirr_raw, long long** sums,
                             int32_t** cnts, int32_t** ray_cnt, float** colmin) {
   size_t vol = (size_t)c->grid[0] * c->grid[1] * c->grid[2] * c->batch;
   size_t svol = (size_t)c->sphere_grid[0] * c->sphere_grid[1] * c->sphere_grid[2] * c->batch;
@@ -489,7 +495,7 @@ static size_t occ_ws_layout(const BtcOccConfig* c, void* ws, uint8_t** smap, uin
   uint8_t* a = cv.take<uint8_t>(svol);
   uint8_t* b = cv.take<uint8_t>(vol);
   uint8_t* m = cv.take<uint8_t>(vol);
-  float* s = cv.take<float>(vol * 9);
+  long long* s = cv.take<long long>(vol * 9);
   int32_t* n = cv.take<int32_t>(vol * 3);
   int32_t* r = cv.take<int32_t>(rays);
   float* cm = cv.take<float>((size_t)c->batch * c->grid[0]);
@@ -546,10 +552,11 @@ extern "C" int btc_occ_targets(const BtcOccConfig* cfg, float* voxels, const int
 
   const size_t vol = (size_t)P.nx * P.ny * P.nz * P.B;
   uint8_t *smap, *occ_raw, *mirr_raw;
-  float *sums, *colmin;
+  long long* sums;
+  float* colmin;
   int32_t *cnts, *ray_cnt;
   occ_ws_layout(cfg, ws, &smap, &occ_raw, &mirr_raw, &sums, &cnts, &ray_cnt, &colmin);
-  float *fore_sum = sums, *mirr_sum = sums + vol * 3, *bm_sum = sums + vol * 6;
+  long long *fore_sum = sums, *mirr_sum = sums + vol * 3, *bm_sum = sums + vol * 6;
   int32_t *fore_cnt = cnts, *mirr_cnt = cnts + vol, *bm_cnt = cnts + vol * 2;
 
   // What the kernels accumulate into starts zeroed: the workspace's smap | occ_raw | mirr_raw | sums | cnts (carved back to back,

@@ -1,5 +1,6 @@
 """bench.py's output contract (one JSON line on stdout; the fields the driver and the judge read), exercised end to end on the
-GPU with a short run: the pipelined schedule, the roofline leg (HIP events per launch) and the CPU-baseline leg all execute."""
+GPU with short runs: the pipelined schedule, and under --full the roofline leg (HIP events per launch) and the CPU-baseline leg."""
+import glob
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _run(*flags):
 
 
 def test_bench_json_line_contract():
-    d = _run("--steps", "4", "--warmup", "2")
+    d = _run("--steps", "4", "--warmup", "2", "--full")
     assert d["metric"].startswith("scenes/s fwd+bwd KITTI-Car bs=2/GPU") and d["unit"] == "scenes/s"
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f32"
@@ -44,6 +45,39 @@ def test_bench_json_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == "scenes/s" and "sample" in c
     assert d["rulebook_hbm_GBps"] > 1
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_outputs(tmp_path):
+    """without --full: the headline measurement only (no secondary legs), and --dump-outputs writes the last timed step's loss and the
+    trained model's floating-point state as float32 .npy files, 64 MB at most -- the same bits in a second run with the same arguments"""
+    out = tmp_path / "outputs"
+    d = _run("--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "scenes/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 50 and abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert d["config"]["priming_steps"] == 63 and d["config"]["level_rows"]["det_voxels"]["median"] > 5000
+    for k in ("roofline", "cpu_baseline", "other_kernels", "rulebook_hbm_GBps"):
+        assert k not in d, k
+    for k in ("in_order_scenes_per_s", "recurring_batches_scenes_per_s", "with_rpn_heads", "with_all_heads", "predicted_scaling_eff"):
+        assert k not in d["config"], k
+    import numpy as np
+    files = sorted(glob.glob(str(out / "*.npy")))
+    names = [os.path.basename(f)[:-4] for f in files]
+    assert "loss" in names and "state.det_modules.backbone_3d.conv_out.0.weight" in names and len(names) > 100
+    assert sum(os.path.getsize(f) for f in files) <= 64 * 2 ** 20
+    loss = np.load(str(out / "loss.npy"))
+    assert loss.dtype == np.float32 and loss.size == 1 and np.isfinite(loss).all() and (loss > 0).all()
+    for f in files:
+        a = np.load(f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+    # bit for bit over the ~66 training steps: every reduction on the path is order-independent except the fused BatchNorm statistics,
+    # whose per-slot fp64 sums take atomic adds from several workgroups (bn_fuse.h, conv_apply_split.hip).  Those sums reach the model
+    # only rounded to fp32 (mean, rstd), so their order shows only when an fp64 sum lies within its last bits of an fp32 rounding
+    # boundary: rare, but if this fails once and passes on a rerun, that is where to look.
+    again = tmp_path / "again"
+    _run("--steps", "3", "--warmup", "1", "--dump-outputs", str(again))
+    assert sorted(os.listdir(str(again))) == sorted(os.path.basename(f) for f in files)
+    for f in files:
+        np.testing.assert_array_equal(np.load(f), np.load(str(again / os.path.basename(f))), err_msg=f)
 
 
 def test_bench_in_order_schedule_still_runs():

@@ -27,10 +27,10 @@ except Exception as e:
 PY
 }
 if has bench; then
-  timeout 500 python bench.py > $out/bench.json 2> $out/bench.err; line $out/bench.json
-  timeout 300 python bench.py --features bf16 --no-cpu-baseline --no-extras > $out/bench_bf16.json 2> $out/bench_bf16.err; line $out/bench_bf16.json
-  timeout 300 python bench.py --workload waymo --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_waymo.json 2> $out/bench_waymo.err; line $out/bench_waymo.json
-  timeout 300 python bench.py --workload waymo --features bf16 --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_waymo_bf16.json 2> $out/bench_waymo_bf16.err; line $out/bench_waymo_bf16.json
+  timeout 500 python bench.py --full > $out/bench.json 2> $out/bench.err; line $out/bench.json
+  timeout 300 python bench.py --full --features bf16 --no-cpu-baseline --no-extras > $out/bench_bf16.json 2> $out/bench_bf16.err; line $out/bench_bf16.json
+  timeout 300 python bench.py --full --workload waymo --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_waymo.json 2> $out/bench_waymo.err; line $out/bench_waymo.json
+  timeout 300 python bench.py --full --workload waymo --features bf16 --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_waymo_bf16.json 2> $out/bench_waymo_bf16.err; line $out/bench_waymo_bf16.json
 fi
 if has pairs; then   # same-box repetitions, 80 steps: the default schedule three times per precision (a process is fast or slow as a whole), in order once
   for f in f32 bf16; do
@@ -85,7 +85,7 @@ if has misc; then
   timeout 300 python tools/straggler.py 64 $out/straggler.json > $out/straggler.log 2>&1; tail -2 $out/straggler.log
   bash tools/gpu_full_heads_prof.sh > $out/full_heads.log 2>&1; cp gpurun_out/full_heads/tail_full.txt $out/full_heads_tail.txt 2>/dev/null
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; tail -1 $out/smoke.txt
-  BTC_BENCH_FORCE_DIST=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_dist1.json 2> $out/bench_dist1.err; line $out/bench_dist1.json
+  BTC_BENCH_FORCE_DIST=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_dist1.json 2> $out/bench_dist1.err; line $out/bench_dist1.json
 fi
 if has tests; then
   timeout 1500 python -m pytest tests -m gpu -q > $out/pytest_gpu.log 2>&1; tail -3 $out/pytest_gpu.log

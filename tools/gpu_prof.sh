@@ -2,9 +2,10 @@
 # bench line + rocprofv3 kernel statistics of the same command (default schedule and the in-order, one-stream schedule)
 tag=${1:-r03a}
 mkdir -p gpurun_out/$tag
+out=$_   # bash: $_ is the last argument of the command above, the folder just made -- keep this line right below the mkdir
 export TMPDIR=/tmp
 cd /root/repo
-[ -n "$SKIP_BENCH" ] || timeout 300 python bench.py --no-cpu-baseline > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err
+[ -n "$SKIP_BENCH" ] || timeout 300 python bench.py --full --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o bench -- python /root/repo/bench.py --no-cpu-baseline --no-roofline --no-extras > /root/repo/gpurun_out/$tag/bench_prof.json 2> /root/repo/gpurun_out/$tag/bench_prof.err)
 find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/$tag/bench_kernel_stats.csv
 find /tmp/prof_$tag -name "*kernel_trace.csv" | head -1 | xargs -I{} python tools/stream_timeline.py {} > gpurun_out/$tag/bench_timeline.txt 2>&1
