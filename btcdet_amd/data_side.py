@@ -36,16 +36,45 @@ def read_bm_template(path, load_point_features=3):
     return obj_points.reshape([-1, load_point_features])[:, :3].astype(np.float32)
 
 
+def _fma_f32(a, b, c):
+    """correctly rounded float32 a * b + c of float32 arrays: the product is exact in float64; the float64 sum's rounding error
+    (TwoSum) decides the one case where rounding that sum to float32 could differ from rounding the exact value (a sum that
+    landed exactly halfway between two floats)"""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    r = s.astype(np.float32)
+    d = s - r.astype(np.float64)
+    other = np.nextafter(r, np.where(d > 0, np.float32(np.inf), np.float32(-np.inf)))
+    past_mid = (d != 0) & (s == (r.astype(np.float64) + other.astype(np.float64)) * 0.5) & (err * d > 0)
+    return np.where(past_mid, other, r)
+
+
 def rotate_points_along_z(points, angle):
-    """points (B, N, 3 + C), angle (B) radians, x towards y; numpy in -> numpy out (computed in fp32 torch, as the reference)"""
+    """points (B, N, 3 + C), angle (B) radians, x towards y; numpy in -> numpy out (fp32, as the reference's torch.matmul).
+    Numpy input: the product with R = [[c, s, 0], [-s, c, 0], [0, 0, 1]] is spelled out in the arithmetic the reference's CPU
+    matmul used where its vectors were recorded (tests/golden/data_side.npz), so that the bits do not depend on the BLAS kernel
+    of the CPU at hand (one without FMA differs in the last bit for about a tenth of the coordinates):
+      3 * 3 * N < 400 (ATen's small-bmm loop): ((0 + x r0j) + y r1j) + z r2j, every step rounded to fp32;
+      larger N (sgemm):                        fma(z, r2j, fma(y, r1j, x r0j))."""
     is_numpy = isinstance(points, np.ndarray)
     pts = torch.from_numpy(points).float() if is_numpy else points
     ang = torch.from_numpy(angle).float() if isinstance(angle, np.ndarray) else angle
     cosa, sina = torch.cos(ang), torch.sin(ang)
     zeros, ones = ang.new_zeros(ang.shape[0]), ang.new_ones(ang.shape[0])
     rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
-    out = torch.cat((torch.matmul(pts[:, :, 0:3], rot), pts[:, :, 3:]), dim=-1)
-    return out.numpy() if is_numpy else out
+    if is_numpy:
+        p, R = pts.numpy(), rot.numpy()
+        x, y, z = p[:, :, 0], p[:, :, 1], p[:, :, 2]
+        r = [[R[:, k, j][:, None] for j in range(3)] for k in range(3)]
+        if 9 * p.shape[1] < 400:
+            cols = [((np.float32(0) + x * r[0][j]) + y * r[1][j]) + z * r[2][j] for j in range(3)]
+        else:
+            cols = [_fma_f32(z, r[2][j], _fma_f32(y, r[1][j], x * r[0][j])) for j in range(3)]
+        return np.concatenate([np.stack(cols, axis=-1), p[:, :, 3:]], axis=-1)
+    return torch.cat((torch.matmul(pts[:, :, 0:3], rot), pts[:, :, 3:]), dim=-1)
 
 
 def global_rotation(gt_boxes, points, rot_range, special_points_lst=()):
