@@ -1067,6 +1067,15 @@ __global__ __launch_bounds__(256) void dense_bwd_k(const float* __restrict__ dde
 template <int NT, bool TRANS_W, int THREADS>
 void launch_apply_t(dim3 grid, size_t lds, hipStream_t stream, bool vec, const float* feat, const float* W, const float* bias,
                     const int32_t* nbr, int n_rows, int K, int Cred, int Cres, float* out, int mirror, const BnFuse& bn) {
+  // the map tile is TM x K int32: past ~148 offsets the launch wants more than 64 KB of LDS (K = BTC_CONV_K_MAX: 157 KB).  Only such
+  // launches ask for the larger limit; the configured layers (K <= 27) never reach this branch.
+  if (lds > 64 * 1024) {
+    static BtcPerDeviceOnce once;
+    btc_once_per_device(once, [] {
+      (void)hipFuncSetAttribute((const void*)conv_apply<NT, TRANS_W, true, 1, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)conv_apply<NT, TRANS_W, false, 1, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+  }
   if (vec) conv_apply<NT, TRANS_W, true, 1, THREADS><<<grid, THREADS, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
   else conv_apply<NT, TRANS_W, false, 1, THREADS><<<grid, THREADS, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
 }
@@ -1276,7 +1285,7 @@ WgradPlan wgrad_plan(int n_out, int K, int Cin, int Cout, int n_in = -1, bool bf
 extern "C" int btc_conv_fwd(const float* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
                             int Cin, int Cout, float* out, void* stream) {
   BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_fwd: bad sizes");
-  BTC_CHECK_ARG(K <= 512, "btc_conv_fwd: K=%d too large for the LDS neighbour tile", K);
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_fwd: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
   return launch_apply<false>(feat, W, bias, nbr_out, n_out, K, Cin, Cout, out, (hipStream_t)stream);
 }
 
@@ -1296,7 +1305,7 @@ extern "C" int btc_conv_dgrad_bf16(const void* dout, const float* W, const int32
 extern "C" int btc_conv_dgrad(const float* dout, const float* W, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
                               float* din, void* stream) {
   BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_in >= 0, "btc_conv_dgrad: bad sizes");
-  BTC_CHECK_ARG(K <= 512, "btc_conv_dgrad: K=%d too large for the LDS neighbour tile", K);
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_dgrad: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
   return launch_apply<true>(dout, W, nullptr, nbr_in, n_in, K, /*Cred=*/Cout, /*Cres=*/Cin, din, (hipStream_t)stream);
 }
 
@@ -1324,7 +1333,8 @@ extern "C" int btc_conv_apply_src(int pass, int operands, const void* src, long 
   // kernels read column K-1-k for offset k and the backward map never exists (same bits as the explicit map: tests)
   const int mirror = pass == BTC_PASS_DGRAD_MIRROR;
   if (mirror) pass = BTC_PASS_DGRAD;
-  BTC_CHECK_ARG(K >= 1 && K <= 512 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_apply_ordered: bad sizes");
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_apply_ordered: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
+  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_apply_ordered: bad sizes");
   BTC_CHECK_ARG(pass == BTC_PASS_FWD || bias == nullptr, "btc_conv_apply_ordered: dgrad takes no bias");
   const int Cred = pass == BTC_PASS_FWD ? Cin : Cout, Cres = pass == BTC_PASS_FWD ? Cout : Cin;
   if (operands == BTC_OPERANDS_BF16) {
@@ -1350,7 +1360,8 @@ extern "C" int btc_conv_apply_src(int pass, int operands, const void* src, long 
 int btc_conv_fwd_stats(int operands, const void* src, long long src_rows, const float* W, const float* bias, const int32_t* nbr, const int32_t* order,
                        int n_rows, int K, int Cin, int Cout, void* dst, const BnFuse& bn, hipStream_t stream, int* fused) {
   *fused = 0;
-  BTC_CHECK_ARG(K >= 1 && K <= 512 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_fwd_stats: bad sizes");
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_bn_relu_fwd: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
+  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_fwd_stats: bad sizes");
   BTC_CHECK_ARG(operands >= BTC_OPERANDS_F32 && operands <= BTC_OPERANDS_F32_SPLIT, "btc_conv_fwd_stats: operands=%d", operands);
   BTC_CHECK_ARG(Cout <= BN_FUSE_CMAX, "btc_conv_fwd_stats: more than %d channels", BN_FUSE_CMAX);
   if (n_rows <= 0) return BTC_OK;
@@ -1415,6 +1426,7 @@ static int wgrad_impl(const float* feat, const float* dout, const int32_t* nbr_o
   // in `ws`, dW untouched -- or 0: dW is complete (no rows: zeros)
   hipStream_t stream = (hipStream_t)stream_;
   BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_wgrad: bad sizes");
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_wgrad: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
   // rows of `feat`: n_in when the backward map comes with it, or when a caller without one states a positive count; a legacy call that
   // passes NULL and 0 (the argument used to be ignored without a map) leaves it unknown -> the fp32-pipe kernels, which need no bound
   // nbr_in == nbr_out (the same pointer, n_in == n_out): a submanifold layer -- its backward map is the forward map with the offset index

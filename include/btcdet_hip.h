@@ -306,6 +306,10 @@ int btc_weights_split3_multi(const float* const* W, void* const* w_split, void* 
 #define BTC_OPERANDS_BF16_ACT 1
 #define BTC_OPERANDS_BF16 2
 #define BTC_OPERANDS_F32_SPLIT 3
+/* the most offsets (K) a layer may have: btc_conv_apply_src / _ordered, btc_conv_fwd / _dgrad, btc_conv_bn_relu_fwd and the weight-gradient
+ * entry points refuse a larger K with BTC_EINVAL.  Past 64 offsets only the register-staged kernel applies a layer; it keeps a 64-row x K
+ * map tile in LDS, and at 512 offsets that tile and the staging buffers fill the 160 KB of a CU. */
+#define BTC_CONV_K_MAX 512
 int btc_row_orders(const int32_t* const* nbrs /* host array of device pointers */, const int32_t* n_rows /* host */,
                    const int32_t* Ks /* host */, int n_maps, int32_t* order /* device, sum n_rows */, void* stream);
 /* the same with the sort keys handed in where they exist: firsts[j] (n_rows[j]) = first present offset of every row of map j (K for a

@@ -7,23 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from conv_ref import f64_conv as _f64_conv
 from oracle import oracle as orc
 from test_hip_core import dev, rand_indices, _rb_both
 
 pytestmark = pytest.mark.gpu
-
-
-def _f64_conv(src, W, nbr, transpose):
-    """float64 reference: dst[i] = sum_k src[nbr[i][k]] @ W[k] (or W[k]^T)"""
-    K = nbr.shape[1]
-    W = W.reshape(K, W.shape[-2], W.shape[-1]).astype(np.float64)
-    s64 = src.astype(np.float64)
-    out = np.zeros((nbr.shape[0], W.shape[1] if transpose else W.shape[2]))
-    for k in range(K):
-        rows = np.nonzero(nbr[:, k] >= 0)[0]
-        if rows.size:
-            out[rows] += s64[nbr[rows, k]] @ (W[k].T if transpose else W[k])
-    return out
 
 
 def _err(a, ref):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from conv_ref import wgrad64 as _ref64
 from test_hip_core import _rb_both, dev, rand_indices
 
 pytestmark = pytest.mark.gpu
@@ -32,18 +33,6 @@ def _no_narrow_kernel():
     assert lib().btc_tune_set(22, 1) == 0
     yield
     assert lib().btc_tune_set(22, 0) == 0
-
-
-def _ref64(feat, dout, nbr_out, K, cin, cout):
-    """dW[k] = sum_i feat[nbr_out[i][k]]^T dout[i] in float64 on the device"""
-    f, d = feat.double(), dout.double()
-    out = torch.zeros((K, cin, cout), dtype=torch.float64, device=feat.device)
-    for k in range(K):
-        col = nbr_out[:, k].long()
-        rows = torch.nonzero(col >= 0).squeeze(1)
-        if rows.numel():
-            out[k] = f[col[rows]].t() @ d[rows]
-    return out
 
 
 def _wgrad(feat, dout, rb, cin, cout, n_in=None, slabs=False):
