@@ -87,6 +87,7 @@ int btc_conv_fwd_stats(int operands, const void* src, long long src_rows, const 
 // conv_apply_bf16.hip: bf16 operands on the bf16 matrix pipe; Wq[k][Cres][Cred] bf16
 int btc_apply_bf16w(const void* src, const void* Wq, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,
                     int Cres, void* dst, hipStream_t stream, int mirror = 0, const struct BnFuse* bn = nullptr);
+// the weight gradient's families outside conv_wgrad.hip, which holds the planner that chooses among them (and the fp32-pipe families)
 // conv_wgrad_x.hip: weight gradient on the bf16 matrix pipe (mode 0: bf16 activations, 1: fp32 activations as three exact bf16 pieces);
 // cg / cc = channels of the gathered / contiguous operand of the row walk
 bool btc_wgrad_x_supported(int mode, int K, int cg, int cc);
@@ -97,7 +98,6 @@ int btc_launch_wgrad_x(int mode, const void* g, const void* c, const int32_t* ma
 // dy gathered through the backward map (mirror: a submanifold layer's forward map, column k' = offset K-1-k'); fp32 matrix pipe
 // ... or with a narrow input (<= 8 channels: the first layers), walked over its OUTPUT rows with the features gathered through nbr_out
 int btc_wgrad_n_kind(int K, int Cin, int Cout);   // 1 narrow result, 2 narrow input, 0 neither
-bool btc_wgrad_n_supported(int K, int Cin, int Cout);   // kind 1
 int btc_wgrad_n_plan(int rows);   // -> slabs
 int btc_launch_wgrad_n(bool bf, const void* walked, const void* gathered, const int32_t* map, int rows, int K, int Cw, int Cn, float* part,
                        int flags /* 1 mirrored map, 2 narrow input (slab written [k][narrow][walked]) */, hipStream_t stream);
@@ -168,6 +168,11 @@ static inline void btc_once_per_device(BtcPerDeviceOnce& o, F&& fn) {
   std::call_once(o.flag[dev >= 0 && dev < BTC_MAX_DEVICES ? dev : 0], fn);
 }
 #endif
+
+// shared by the fp32-pipe sparse-conv kernels (sparse_conv.hip: apply; conv_wgrad.hip: weight gradient)
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // an MFMA accumulator tile's four rows of one lane
+constexpr int TM = 64;                                     // rows per workgroup tile
+__host__ __device__ constexpr int ldb_of(int nt) { return nt * 16 + (((nt * 16) % 32 == 0) ? 16 : 0); }   // LDS row pitch of nt 16-column tiles
 
 static inline int btc_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t btc_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

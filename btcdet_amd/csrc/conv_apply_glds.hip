@@ -17,8 +17,6 @@
 
 #include <mutex>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 __device__ float g_zero_row[64];  // zero-initialised; the source of gathers for absent neighbours

@@ -23,7 +23,6 @@
 #include "btc_common.h"
 #include "bn_fuse.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {

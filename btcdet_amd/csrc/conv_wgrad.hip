@@ -1,0 +1,1020 @@
+// Sparse convolution weight gradient for gfx950: the fp32-matrix-pipe kernels (offset-major conv_wgrad_partial / _partial_p, row-stationary
+// conv_wgrad_rows / _rows_p), the slab reductions, and the ONE planner that picks a kernel family and its slab count for every
+// weight-gradient call -- the families of conv_wgrad_x.hip (bf16 matrix pipe) and conv_wgrad_n.hip (narrow layers) included.
+//
+// Every family writes S partial sums ("slabs") of K * Cin * Cout floats into the caller's workspace; wgrad_reduce adds them up in slab
+// order (deterministic).  btc_conv_wgrad_ws_bytes is computed from the same per-family plans the launch uses (wgrad_max_slabs).
+#include "btc_common.h"
+
+namespace {
+
+// dW partial: part[s][k][ci][co] = sum over the split's rows of feat[nbr[i][k]][ci] * dout[i][co]
+// block = (k, split, tile of 64 Cin x NT*16 Cout); wave w owns dW rows [m0 + 16w, m0 + 16w + 16)
+constexpr int WG_LDA = 64 + 16;
+template <int NT, bool BF>
+__global__ __launch_bounds__(256) void conv_wgrad_partial(const float* __restrict__ feat, const float* __restrict__ dout,
+                                                          const int32_t* __restrict__ nbr, int n_out, int K, int Cin,
+                                                          int Cout, int tiles_per_split, int n_cblk, float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LDB = ldb_of(NT);
+  float* As = (float*)smem;       // [TM][WG_LDA]  gathered input rows, 64 channels
+  float* Ds = As + TM * WG_LDA;   // [TM][LDB]     dout rows, NT*16 channels
+  int32_t* s_j = (int32_t*)(Ds + TM * LDB);  // [TM] (kept inside the one dynamic LDS array)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x, split = blockIdx.y;
+  const int m0 = (blockIdx.z / n_cblk) * 64;
+  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
+  const int n_tiles = (n_out + TM - 1) / TM;
+  const int t_begin = split * tiles_per_split;
+  const int t_end = min(n_tiles, t_begin + tiles_per_split);
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int kq = lane >> 4;
+  const bool wave_live = (m0 + wave * 16) < Cin;
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int row0 = t * TM;
+    int j = -1;
+    if (tid < TM && row0 + tid < n_out) j = nbr[(size_t)(row0 + tid) * K + k];
+    if (tid < TM) s_j[tid] = j;
+    if (!__syncthreads_or(j >= 0)) continue;
+    // all loads of a thread are issued before the first LDS store (one memory latency per tile)
+    if (((Cin | Cout) & 3) == 0) {
+      float4 va[4], vd[NT];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
+        int jj = s_j[r];
+        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c)
+                                               : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
+        float* d = As + r * WG_LDA + c;
+        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
+      }
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+        float* d = Ds + r * LDB + c;
+        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
+      }
+    } else {
+      float va[16], vd[NT * 4];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        int e = i * 256 + tid, r = e >> 6, c = e & 63;
+        int jj = s_j[r];
+        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld1<BF>(feat, (size_t)jj * Cin + m0 + c) : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < NT * 4; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
+        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld1<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c) : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        int e = i * 256 + tid, r = e >> 6, c = e & 63;
+        As[r * WG_LDA + c] = va[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NT * 4; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
+        Ds[r * LDB + c] = vd[i];
+      }
+    }
+    __syncthreads();
+    if (wave_live) {
+#pragma unroll 4
+      for (int q = 0; q < TM / 4; ++q) {
+        float a = As[(q * 4 + kq) * WG_LDA + wave * 16 + (lane & 15)];
+        const float* bp = Ds + (q * 4 + kq) * LDB + (lane & 15);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[nt * 16], acc[nt], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  float* P = part + ((size_t)split * K + k) * Cin * Cout;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int col = n0 + nt * 16 + (lane & 15);
+    if (col >= Cout) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int ci = m0 + wave * 16 + kq * 4 + r;
+      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
+    }
+  }
+}
+
+// conv_wgrad_partial for channel counts that are multiples of 4, with
+//  * the next tile's loads in flight during this tile's MFMAs: the map column entry of tile t + 1 is read while tile t is being
+//    staged, its gathered rows and dOut rows are requested right after tile t's tiles are visible in LDS and sit in registers
+//    until tile t's MFMAs are done (same LDS footprint, same two barriers per tile);
+//  * per-tile packing: only the rows of the tile that HAVE the offset are staged, packed to the front of the LDS tiles (a wave
+//    ballot over the column gives every live row its slot), and the reduction runs over ceil(m / 4) 4-row steps instead of 16.
+//    Both operands are gathered per offset here anyway, so packing costs no indirection in the MFMA loop.  At the wide layers
+//    that land on this kernel (128 -> 128, 256 -> 128 on the 8x-downsampled level) 55 % of the (row, offset) slots are live.
+// Skipped terms are exact zeros; dW differs from the unpacked sum only in how rows group into 4-row MFMA steps.
+template <int NT, bool BF>
+__global__ __launch_bounds__(256) void conv_wgrad_partial_p(const float* __restrict__ feat, const float* __restrict__ dout,
+                                                            const int32_t* __restrict__ nbr, int n_out, int K, int Cin, int Cout,
+                                                            int tiles_per_split, int n_cblk, float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LDB = ldb_of(NT);
+  float* As = (float*)smem;       // [TM][WG_LDA]  gathered input rows (packed), 64 channels
+  float* Ds = As + TM * WG_LDA;   // [TM][LDB]     dout rows (packed), NT*16 channels
+  int32_t* s_src = (int32_t*)(Ds + TM * LDB);  // [2][TM] input row of packed slot t (-1: padding of the last 4-row step)
+  int32_t* s_dst = s_src + 2 * TM;             // [2][TM] output row of packed slot t
+  int32_t* s_m = s_dst + 2 * TM;               // [2] live rows of the tile
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x, split = blockIdx.y;
+  const int m0 = (blockIdx.z / n_cblk) * 64;
+  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
+  const int n_tiles = (n_out + TM - 1) / TM;
+  const int t_begin = split * tiles_per_split;
+  const int t_end = min(n_tiles, t_begin + tiles_per_split);
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int kq = lane >> 4;
+  const bool wave_live = (m0 + wave * 16) < Cin;
+
+  float4 va[4], vd[NT];
+  auto load_j = [&](int t) {   // wave 0: map column entry of row `lane` of tile t
+    const int row = t * TM + lane;
+    return (wave == 0 && t < t_end && row < n_out) ? nbr[(size_t)row * K + k] : -1;
+  };
+  auto pack = [&](int t, int j, int b) {   // wave 0: packed slots of tile t into buffer b
+    if (wave != 0) return;
+    const unsigned long long live = __ballot(j >= 0);
+    const int m = __popcll(live);
+    if (j >= 0) {
+      const int slot = __popcll(live & ((1ull << lane) - 1ull));
+      s_src[b * TM + slot] = j;
+      s_dst[b * TM + slot] = t * TM + lane;
+    }
+    if (lane >= m && lane < ((m + 3) & ~3)) {
+      s_src[b * TM + lane] = -1;
+      s_dst[b * TM + lane] = -1;
+    }
+    if (lane == 0) s_m[b] = m;
+  };
+  auto load_tile = [&](int b) {
+    const int m4 = (s_m[b] + 3) & ~3;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
+      const int jj = r < m4 ? s_src[b * TM + r] : -1;
+      va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+      const int ro = r < m4 ? s_dst[b * TM + r] : -1;
+      vd[i] = (ro >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)ro * Cout + n0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto store_tile = [&](int m4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
+      if (r < m4) {
+        float* d = As + r * WG_LDA + c;
+        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+      if (r < m4) {
+        float* d = Ds + r * LDB + c;
+        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
+      }
+    }
+  };
+
+  // prologue: the first tile's column and loads, the second tile's column
+  int m4 = 0, jn = -1;
+  if (t_begin < t_end) {
+    pack(t_begin, load_j(t_begin), 0);
+    __syncthreads();
+    m4 = (s_m[0] + 3) & ~3;
+    if (m4) load_tile(0);
+    jn = load_j(t_begin + 1);
+  }
+  for (int t = t_begin; t < t_end; ++t) {
+    const int cur = (t - t_begin) & 1;
+    if (m4) store_tile(m4);            // tile t: registers -> LDS (the previous tile's MFMAs ended at the barrier below)
+    pack(t + 1, jn, cur ^ 1);          // tile t + 1's packed slots
+    __syncthreads();                   // tile t in LDS; everyone sees tile t + 1's slots
+    const int m4_next = (s_m[cur ^ 1] + 3) & ~3;
+    if (m4_next) load_tile(cur ^ 1);   // in flight during the MFMAs below
+    jn = load_j(t + 2);
+    if (m4 && wave_live) {
+      const int steps = m4 >> 2;
+      const float* ap = As + kq * WG_LDA + wave * 16 + (lane & 15);
+      const float* bp = Ds + kq * LDB + (lane & 15);
+#pragma unroll 4
+      for (int q = 0; q < steps; ++q) {
+        const float a = ap[q * 4 * WG_LDA];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[q * 4 * LDB + nt * 16], acc[nt], 0, 0, 0);
+      }
+    }
+    __syncthreads();   // MFMAs of tile t done: the LDS tiles may be overwritten
+    m4 = m4_next;
+  }
+  float* P = part + ((size_t)split * K + k) * Cin * Cout;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int col = n0 + nt * 16 + (lane & 15);
+    if (col >= Cout) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int ci = m0 + wave * 16 + kq * 4 + r;
+      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Row-stationary weight gradient for the large-N / small-C layers (the occupancy branch: up to 210 K rows at 32
+// channels).  A persistent workgroup walks row tiles; per tile the dOut rows and the neighbour-map rows are loaded
+// ONCE (coalesced, row-major) and the K offsets are processed in phases of KB gathered input tiles; the whole
+// dW slab of the workgroup's offset group (PH*KB offsets x Cin x Cout) lives in MFMA accumulators for the entire
+// walk and is written out once.  (The offset-major kernel below re-reads dOut K times and reads the map column-wise.)
+//   MT, NT : 16-wide tiles of Cin / Cout;  KB : offsets per LDS phase;  PH : phases per offset group
+// ------------------------------------------------------------------------------------------------------------
+template <int MT, int NT, int KB, int PH, bool BF>
+__global__ __launch_bounds__(256) void conv_wgrad_rows(const float* __restrict__ feat, const float* __restrict__ dout,
+                                                       const int32_t* __restrict__ nbr, const int32_t* __restrict__ order, int n_out, int K,
+                                                       int Cin, int Cout, float* __restrict__ part, int swap, int dbg) {
+  // order (optional, row_order.hip): tile slot t works on map row order[t]; rows with the same offsets share tiles, so fewer
+  // offset phases per tile are live.  dW is the fp32 sum over rows in walk order.
+  // Naming follows the un-swapped case: `feat` = gathered operand (Cin channels, via the map), `dout` = contiguous
+  // operand (Cout channels), one tile per 64 map rows.  swap = 1: the walk is over the INPUT rows instead (map =
+  // nbr_in, gathered = dOut, contiguous = features) -- used when the layer has far fewer input than output rows
+  // (transposed / dilating convs) -- and the slab is written transposed so that dW keeps the [K][Cin][Cout] layout.
+  constexpr int TPP = KB * MT * NT / 4;  // accumulator tiles per wave per phase
+  static_assert(KB * MT * NT % 4 == 0, "phase tiles must split evenly over the 4 waves");
+  constexpr int LDA = ldb_of(MT), LDB = ldb_of(NT);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* As = (float*)smem;                       // [KB][TM][LDA]
+  float* Ds = As + KB * TM * LDA;                 // [TM][LDB]
+  int32_t* s_nbr = (int32_t*)(Ds + TM * LDB);     // [TM][K]
+  int32_t* s_kact = s_nbr + TM * K;               // [K]
+  int32_t* s_row = s_kact + K;                    // [TM] map row of each tile slot, -1 past the end
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+  const int kg0 = blockIdx.y * (PH * KB);         // first offset of this workgroup's group
+  const int n_tiles = (n_out + TM - 1) / TM;
+
+  f32x4 acc[PH * TPP];
+#pragma unroll
+  for (int t = 0; t < PH * TPP; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int row0 = tile * TM;
+    for (int e = tid; e < K; e += 256) s_kact[e] = 0;
+    if (tid < TM) s_row[tid] = (row0 + tid < n_out) ? (order ? order[row0 + tid] : row0 + tid) : -1;
+    __syncthreads();
+    for (int e = tid; e < TM * K; e += 256) {
+      const int rloc = e / K, kk = e - rloc * K;
+      const int gr = s_row[rloc];
+      const int v = gr >= 0 ? nbr[(long long)gr * K + kk] : -1;
+      s_nbr[e] = v;
+      if (v >= 0) s_kact[kk] = 1;
+    }
+    // dOut tile: all loads of a thread are issued before the first LDS store (one latency, not one per element)
+    if ((Cout & 3) == 0) {
+      float4 v[NT];
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+        const int gr = s_row[r];
+        v[i] = (gr >= 0 && c < Cout) ? btc_ld4<BF>(dout, (size_t)gr * Cout + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
+        float* d = Ds + r * LDB + c;
+        d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
+      }
+    } else {
+      float v[NT * 4];
+#pragma unroll
+      for (int i = 0; i < NT * 4; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
+        const int gr = s_row[r];
+        v[i] = (gr >= 0 && c < Cout) ? btc_ld1<BF>(dout, (size_t)gr * Cout + c) : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < NT * 4; ++i) {
+        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
+        Ds[r * LDB + c] = v[i];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < PH; ++p) {
+      const int k0 = kg0 + p * KB;
+      int any = 0;
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) any |= (k0 + kb < K) ? s_kact[k0 + kb] : 0;
+      if (!any) continue;  // block-uniform
+      // gather KB input tiles; loads batched in registers as above
+      if ((Cin & 3) == 0) {
+        float4 v[KB * MT];
+#pragma unroll
+        for (int i = 0; i < KB * MT; ++i) {
+          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
+          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
+          if (dbg & 8) j = -1;  // timing experiments only (BTC_TUNE_APPLY_DEBUG, tools/wgrad_bench.py): no gathers
+          v[i] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < KB * MT; ++i) {
+          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
+          float* d = As + (kb * TM + r) * LDA + c;
+          d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
+        }
+      } else {
+        float v[KB * MT * 4];
+#pragma unroll
+        for (int i = 0; i < KB * MT * 4; ++i) {
+          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
+          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
+          v[i] = (j >= 0 && c < Cin) ? btc_ld1<BF>(feat, (size_t)j * Cin + c) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < KB * MT * 4; ++i) {
+          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
+          As[(kb * TM + r) * LDA + c] = v[i];
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < TPP; ++q) {
+        if (dbg & 4) continue;       // timing experiments only: no MFMA phase
+        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt)
+        const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
+        const float* ap = As + (size_t)kb * TM * LDA + mt * 16 + (lane & 15);
+        const float* bp = Ds + nt * 16 + (lane & 15);
+        f32x4 a4 = acc[p * TPP + q];
+#pragma unroll 4
+        for (int s = 0; s < TM / 4; ++s)
+          a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[(s * 4 + kq) * LDA], bp[(s * 4 + kq) * LDB], a4, 0, 0, 0);
+        acc[p * TPP + q] = a4;
+      }
+      __syncthreads();
+    }
+  }
+  // write this workgroup's slab: part[blockIdx.x][k][ci][co]
+  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
+#pragma unroll
+  for (int p = 0; p < PH; ++p)
+#pragma unroll
+    for (int q = 0; q < TPP; ++q) {
+      const int l = q * 4 + wave;
+      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
+      const int k = kg0 + p * KB + kb;
+      const int co = nt * 16 + (lane & 15);
+      if (k >= K || co >= Cout) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int ci = mt * 16 + kq * 4 + r;
+        if (ci < Cin) {
+          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
+          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];  // here ci indexes dOut channels, co feature channels
+        }
+      }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// conv_wgrad_rows, software-pipelined (gathered-operand channel counts that are multiples of 4).  tools/wgrad_bench.py on the
+// kernel above: removing the MFMA phase halves its time, removing the gathers changes nothing -- a workgroup alternates
+// between a staging round (issue the loads, wait one L2 / HBM latency, store to LDS, barrier: ~1.8 us) and an MFMA phase of
+// about the same length, and only the other workgroup of the CU fills the holes.  Here
+//  * the loads of item g + 1 (the gathered rows of the next phase; the map rows of the tile after next) are issued right
+//    after item g's barrier and land in registers while item g's MFMAs run; they are stored to the OTHER LDS buffer at the
+//    top of item g + 1: one barrier per item, no exposed load latency;
+//  * the contiguous operand never goes through LDS: 4 % NT == 0, so a wave's accumulator tiles all share ONE 16-column block
+//    (nt = wave % NT), and its MFMA B fragments for the 16 4-row steps of a tile are 16 registers, loaded once per tile
+//    (prefetched during the previous tile's last phase) and reused by every offset of the group.  Half the LDS reads of the
+//    MFMA loop, and the LDS footprint drops to the double-buffered gather tile: 41-64 KB, two to three workgroups per CU.
+// Same tiles, same 4-row MFMA steps, same order over rows as the kernel above.  Items are all (tile, phase) pairs: a phase
+// none of whose offsets occurs in the tile costs zeros -- at 64-row tiles that is < 10 % of the phases of the layers this
+// kernel takes.
+//   LDS: As[2][KB][TM][LDA] | s_nbr[3][TM][NOFF] (the group's offsets only) | s_row[3][TM]
+// ------------------------------------------------------------------------------------------------------------
+template <int MT, int NT, int KB, int PH, bool BF>
+__global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict__ feat, const float* __restrict__ dout,
+                                                         const int32_t* __restrict__ nbr, const int32_t* __restrict__ order, int n_out, int K,
+                                                         int Cin, int Cout, float* __restrict__ part, int swap) {
+  constexpr int TPP = KB * MT * NT / 4;
+  static_assert(KB * MT * NT % 4 == 0, "phase tiles must split evenly over the 4 waves");
+  static_assert(4 % NT == 0, "a wave's tiles must share one column block");
+  constexpr int LDA = ldb_of(MT);
+  constexpr int NOFF = PH * KB;
+  constexpr int NV = (TM * NOFF + 255) / 256;   // map entries per thread and tile
+  constexpr int NS = TM / 4;                    // 4-row MFMA steps per tile
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* As = (float*)smem;                              // [2][KB][TM][LDA]
+  int32_t* s_nbr = (int32_t*)(As + 2 * KB * TM * LDA);   // [3][TM][NOFF]
+  int32_t* s_row = s_nbr + 3 * TM * NOFF;                // [3][TM]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+  const int kg0 = blockIdx.y * NOFF;
+  const int n_tiles = (n_out + TM - 1) / TM;
+  const int nt_wg = ((int)blockIdx.x < n_tiles) ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;   // tiles of this workgroup
+  const int bcol = (wave % NT) * 16 + (lane & 15);   // this lane's column of the contiguous operand
+
+  f32x4 acc[PH * TPP];
+#pragma unroll
+  for (int t = 0; t < PH * TPP; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  int nv[NV], nrow = -1;            // the map rows (this group's offsets) and row ids of a tile, in flight
+  float4 gv[KB * MT];               // the gathered rows of an item, in flight
+  float bcur[NS], bnext[NS];        // B fragments of the tile / of the next tile (in flight)
+
+  auto load_map = [&](int i) {      // tile i of this workgroup -> registers
+    const int row0 = (blockIdx.x + i * gridDim.x) * TM;
+    if (tid < TM) nrow = (row0 + tid < n_out) ? (order ? order[row0 + tid] : row0 + tid) : -1;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int e = u * 256 + tid, r = e / NOFF, o = e - r * NOFF;
+      int v = -1;
+      if (e < TM * NOFF && row0 + r < n_out && kg0 + o < K) {
+        const int gr = order ? order[row0 + r] : row0 + r;
+        v = nbr[(long long)gr * K + kg0 + o];
+      }
+      nv[u] = v;
+    }
+  };
+  auto store_map = [&](int i) {
+    int32_t* dn = s_nbr + (i % 3) * TM * NOFF;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int e = u * 256 + tid;
+      if (e < TM * NOFF) dn[e] = nv[u];
+    }
+    if (tid < TM) s_row[(i % 3) * TM + tid] = nrow;
+  };
+  auto load_b = [&](int i) {        // B fragments of tile i (its row ids are in LDS): row 4 s + kq, column bcol
+    const int32_t* rows = s_row + (i % 3) * TM + kq;
+#pragma unroll
+    for (int s2 = 0; s2 < NS; ++s2) {
+      const int gr = rows[s2 * 4];
+      bnext[s2] = (gr >= 0 && bcol < Cout) ? btc_ld1<BF>(dout, (size_t)gr * Cout + bcol) : 0.f;
+    }
+  };
+  // bf16 activations (the launcher guarantees Cin % 8 == 0 for these instances): 16-byte loads of 8 channels -- half the load
+  // instructions of the 4-channel walk and half its staging registers (216 -> 152 VGPRs for the 64 x 64 shape: a third workgroup
+  // per CU) -- widened to fp32 on the way into LDS
+  constexpr int UPR8 = MT * 2;                             // 8-channel units per gathered row
+  constexpr int NU8 = BF ? (KB * TM * UPR8 + 255) / 256 : 1;   // units per thread and item
+  uint4 gq[NU8];
+  constexpr bool wide = BF;
+  auto load_g = [&](int i, int p) { // the gathered rows of phase p of tile i
+    const int32_t* mp = s_nbr + (i % 3) * TM * NOFF + p * KB;
+    if (wide) {
+#pragma unroll
+      for (int u = 0; u < NU8; ++u) {
+        const int e = u * 256 + tid, c8 = e % UPR8, r = (e / UPR8) % TM, kb = e / (UPR8 * TM);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (e < KB * TM * UPR8) {
+          const int j = mp[r * NOFF + kb];
+          if (j >= 0 && c8 * 8 < Cin) v = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(feat) + (size_t)j * Cin + c8 * 8);
+        }
+        gq[u] = v;
+      }
+      return;
+    }
+#pragma unroll
+    for (int u = 0; u < KB * MT; ++u) {
+      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
+      const int j = mp[r * NOFF + kb];
+      gv[u] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto store_g = [&](int buf) {
+    float* A = As + buf * KB * TM * LDA;
+    if (wide) {
+#pragma unroll
+      for (int u = 0; u < NU8; ++u) {
+        const int e = u * 256 + tid, c8 = e % UPR8, r = (e / UPR8) % TM, kb = e / (UPR8 * TM);
+        if (e < KB * TM * UPR8) {
+          float* d = A + (kb * TM + r) * LDA + c8 * 8;
+          const unsigned w[4] = {gq[u].x, gq[u].y, gq[u].z, gq[u].w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            d[2 * q] = __uint_as_float(w[q] << 16);
+            d[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
+          }
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int u = 0; u < KB * MT; ++u) {
+      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
+      float* d = A + (kb * TM + r) * LDA + c;
+      d[0] = gv[u].x; d[1] = gv[u].y; d[2] = gv[u].z; d[3] = gv[u].w;
+    }
+  };
+
+  if (nt_wg > 0) {
+    load_map(0);
+    store_map(0);
+    if (nt_wg > 1) {
+      load_map(1);
+      store_map(1);
+    }
+    __syncthreads();
+    load_b(0);
+    load_g(0, 0);
+  }
+  int buf = 0;
+  for (int i = 0; i < nt_wg; ++i) {
+#pragma unroll
+    for (int p = 0; p < PH; ++p) {
+      store_g(buf);
+      if (p == 0) {
+#pragma unroll
+        for (int s2 = 0; s2 < NS; ++s2) bcur[s2] = bnext[s2];
+      }
+      // the map rows that were loaded during the previous item: tile i + 2 (PH > 1: loaded at this tile's phase 0) or
+      // tile i + 1 (PH == 1: loaded during tile i - 1); tiles 0 and 1 come from the prologue
+      if (PH > 1 ? (p == 1 && i + 2 < nt_wg) : (i >= 1 && i + 1 < nt_wg)) store_map(PH > 1 ? i + 2 : i + 1);
+      __syncthreads();
+      // ---- loads for the next item, in flight during this item's MFMAs
+      if (p + 1 < PH) {
+        load_g(i, p + 1);
+      } else if (i + 1 < nt_wg) {
+        load_b(i + 1);
+        load_g(i + 1, 0);
+      }
+      if (PH > 1 ? (p == 0 && i + 2 < nt_wg) : (i + 2 < nt_wg)) load_map(i + 2);
+      // ---- MFMAs of item (i, p)
+      const float* A = As + buf * KB * TM * LDA;
+#pragma unroll
+      for (int q = 0; q < TPP; ++q) {
+        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt), nt == wave % NT
+        const int mt = (l / NT) % MT, kb = l / (NT * MT);
+        const float* ap = A + (size_t)kb * TM * LDA + mt * 16 + (lane & 15) + kq * LDA;
+        f32x4 a4 = acc[p * TPP + q];
+#pragma unroll
+        for (int s2 = 0; s2 < NS; ++s2) a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[s2 * 4 * LDA], bcur[s2], a4, 0, 0, 0);
+        acc[p * TPP + q] = a4;
+      }
+      buf ^= 1;
+    }
+  }
+  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
+#pragma unroll
+  for (int p = 0; p < PH; ++p)
+#pragma unroll
+    for (int q = 0; q < TPP; ++q) {
+      const int l = q * 4 + wave;
+      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
+      const int k = kg0 + p * KB + kb;
+      const int co = nt * 16 + (lane & 15);
+      if (k >= K || co >= Cout) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int ci = mt * 16 + kq * 4 + r;
+        if (ci < Cin) {
+          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
+          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];
+        }
+      }
+    }
+}
+
+// dW[e] = sum_s part[s][e] in slab order (deterministic); 8 loads in flight per thread
+__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ part, int S, long long count,
+                                                    float* __restrict__ dW) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  float s = 0.f;
+  int q = 0;
+  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
+  // additions is the slab order either way)
+  for (; q + 16 <= S; q += 16) {
+    float v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = part[(size_t)(q + u) * count + e];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) s += v[u];
+  }
+  for (; q + 8 <= S; q += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(q + u) * count + e];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; q < S; ++q) s += part[(size_t)q * count + e];
+  dW[e] = s;
+}
+
+// the slab reductions of MANY layers in one launch (btc_wgrad_reduce_multi: every weight gradient of a backward pass whose dW nobody
+// reads before the side stream's join): block b works on job j with block0[j] <= b < block0[j + 1]; same sums, same order as wgrad_reduce
+struct ReduceJobs {
+  const float* part[BTC_WGRAD_MULTI_MAX];
+  float* dW[BTC_WGRAD_MULTI_MAX];
+  long long count[BTC_WGRAD_MULTI_MAX];
+  int S[BTC_WGRAD_MULTI_MAX];
+  int block0[BTC_WGRAD_MULTI_MAX + 1];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void wgrad_reduce_multi(const ReduceJobs jobs) {
+  int j = 0;
+  while (j + 1 < jobs.n && (int)blockIdx.x >= jobs.block0[j + 1]) ++j;   // (uniform: scalar loop over <= 64 entries)
+  const long long e = (long long)((int)blockIdx.x - jobs.block0[j]) * 256 + threadIdx.x;
+  const long long count = jobs.count[j];
+  if (e >= count) return;
+  const float* __restrict__ part = jobs.part[j];
+  const int S = jobs.S[j];
+  float s = 0.f;
+  int q = 0;
+  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
+  // additions is the slab order either way)
+  for (; q + 16 <= S; q += 16) {
+    float v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = part[(size_t)(q + u) * count + e];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) s += v[u];
+  }
+  for (; q + 8 <= S; q += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(q + u) * count + e];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; q < S; ++q) s += part[(size_t)q * count + e];
+  jobs.dW[j][e] = s;
+}
+
+// ---- host side: one planner (wgrad_choose) decides everything about a call; btc_conv_wgrad_ws_bytes asks the same per-family plans ----
+
+// what the caller has
+struct WgradCall {
+  int n_out, K, Cin, Cout;
+  int n_in;      // rows of the backward map, < 0: there is none (a submanifold layer's mirrored forward map counts as none: the kernels
+                 // that walk the output rows take nothing from it)
+  int n_feat;    // rows of `feat`, < 0: unknown
+  bool mirror;   // nbr_in == nbr_out: the backward map is the forward map with the offset index mirrored (rulebook.hip)
+};
+
+// One side of the rulebook as a row walk: the walked operand's rows are read once, in order, the other operand's rows are gathered
+// through the map.  swap = 0: the OUTPUT rows (walked dout, gathered feat, nbr_out, order_out); swap = 1: the INPUT rows (walked feat,
+// gathered dout, nbr_in or the mirrored nbr_out, order_in) and the slab is written transposed, so dW keeps its [K][Cin][Cout] layout.
+struct WgradWalk {
+  int swap, rows;
+  int Cg, Cc;    // channels of the gathered / the walked (contiguous) operand
+};
+
+struct WgradArgs {   // the operands of the chosen walk
+  const float *g, *c;
+  const int32_t *map, *ord;
+  int K;
+  float* part;
+  hipStream_t stream;
+};
+
+enum WgradFamily { WG_N, WG_X, WG_ROWS_P, WG_ROWS, WG_PARTIAL_P, WG_PARTIAL };
+
+struct WgradLaunch {
+  WgradFamily family;
+  int S;                                                 // slabs the launch writes
+  WgradWalk walk;
+  void (*fn)(const WgradLaunch&, const WgradArgs&);      // fp32-pipe families: the template instance
+  size_t lds;                                            // ... and its dynamic LDS bytes
+  int groups;                                            // rows_p / rows: offset groups
+  int n_cblk, n_mblk, tiles_per_split;                   // partial_p / partial
+};
+
+template <int MT, int NT, int KB, int PH, bool BF>
+void launch_wgrad_rows_p(const WgradLaunch& L, const WgradArgs& a) {
+  static BtcPerDeviceOnce once;   // launches come from the training thread, the autograd thread and the prefetch thread
+  btc_once_per_device(once, [] {
+    (void)hipFuncSetAttribute((const void*)conv_wgrad_rows_p<MT, NT, KB, PH, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  });
+  conv_wgrad_rows_p<MT, NT, KB, PH, BF><<<dim3(L.S, L.groups), 256, L.lds, a.stream>>>(a.g, a.c, a.map, a.ord, L.walk.rows, a.K, L.walk.Cg, L.walk.Cc,
+                                                                                    a.part, L.walk.swap);
+}
+
+template <int MT, int NT, int KB, int PH, bool BF>
+void launch_wgrad_rows(const WgradLaunch& L, const WgradArgs& a) {
+  conv_wgrad_rows<MT, NT, KB, PH, BF><<<dim3(L.S, L.groups), 256, L.lds, a.stream>>>(a.g, a.c, a.map, a.ord, L.walk.rows, a.K, L.walk.Cg, L.walk.Cc, a.part,
+                                                                                  L.walk.swap, btc_tune_get(BTC_TUNE_APPLY_DEBUG));
+}
+
+template <int NT, bool BF, bool PIPE>
+void launch_wgrad_partial(const WgradLaunch& L, const WgradArgs& a) {
+  const dim3 grid(a.K, L.S, L.n_mblk * L.n_cblk);
+  const WgradWalk& w = L.walk;   // (the output rows: Cg = Cin, Cc = Cout)
+  if (PIPE) conv_wgrad_partial_p<NT, BF><<<grid, 256, L.lds, a.stream>>>(a.g, a.c, a.map, w.rows, a.K, w.Cg, w.Cc, L.tiles_per_split, L.n_cblk, a.part);
+  else conv_wgrad_partial<NT, BF><<<grid, 256, L.lds, a.stream>>>(a.g, a.c, a.map, w.rows, a.K, w.Cg, w.Cc, L.tiles_per_split, L.n_cblk, a.part);
+}
+
+// ---- the instance tables (each macro spells the template instances of one table row, nothing else) ----
+// rows_p / rows: (MT, NT) 16-wide tiles of the gathered / walked channels -> KB offsets per LDS phase, PH phases per offset group
+struct RowsTile {
+  int mt, nt, kb, ph;
+  void (*fn[2][4])(const WgradLaunch&, const WgradArgs&);   // [bf16 activations][PH variant]
+};
+// conv_wgrad_rows_p: variants PH = ph, ph / 2 (its own (KB, PH) per tile shape: the B fragments live in registers, LDS holds the
+// double-buffered gather tile only)
+#define ROWS_P_TILE(MT, NT, KB, PH)                                                                                        \
+  {MT, NT, KB, PH, {{launch_wgrad_rows_p<MT, NT, KB, PH, false>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, false>},         \
+                    {launch_wgrad_rows_p<MT, NT, KB, PH, true>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, true>}}}
+const RowsTile ROWS_P_TILES[] = {ROWS_P_TILE(1, 1, 4, 4), ROWS_P_TILE(2, 1, 2, 8), ROWS_P_TILE(1, 2, 4, 4), ROWS_P_TILE(2, 2, 2, 8),
+                                 ROWS_P_TILE(3, 2, 2, 4), ROWS_P_TILE(2, 4, 2, 4), ROWS_P_TILE(4, 2, 1, 8), ROWS_P_TILE(4, 4, 1, 4)};
+#undef ROWS_P_TILE
+// conv_wgrad_rows: variants PH = 1, 2, 4, 7 and ph = 0 (the work split picks one), or the one PH named
+#define ROWS_TILE(MT, NT, KB)                                                                                                                          \
+  {MT, NT, KB, 0, {{launch_wgrad_rows<MT, NT, KB, 1, false>, launch_wgrad_rows<MT, NT, KB, 2, false>, launch_wgrad_rows<MT, NT, KB, 4, false>,        \
+                    launch_wgrad_rows<MT, NT, KB, 7, false>},                                                                                         \
+                   {launch_wgrad_rows<MT, NT, KB, 1, true>, launch_wgrad_rows<MT, NT, KB, 2, true>, launch_wgrad_rows<MT, NT, KB, 4, true>,           \
+                    launch_wgrad_rows<MT, NT, KB, 7, true>}}}
+const RowsTile ROWS_TILES[] = {{1, 1, 8, 4, {{nullptr, nullptr, launch_wgrad_rows<1, 1, 8, 4, false>}, {nullptr, nullptr, launch_wgrad_rows<1, 1, 8, 4, true>}}},
+                               ROWS_TILE(2, 1, 4), ROWS_TILE(1, 2, 4), ROWS_TILE(2, 2, 4), ROWS_TILE(3, 2, 2), ROWS_TILE(2, 4, 2), ROWS_TILE(4, 2, 2),
+                               ROWS_TILE(4, 4, 1)};
+#undef ROWS_TILE
+constexpr int N_ROWS_TILES = sizeof(ROWS_TILES) / sizeof(ROWS_TILES[0]);
+static_assert(sizeof(ROWS_P_TILES) == sizeof(ROWS_TILES), "the two row-stationary kernels take the same tile shapes, in the same order");
+// partial_p / partial: NT = 1, 2, 4, 8 16-column tiles of Cout per workgroup
+#define PARTIAL_NT(BF, PIPE) \
+  {launch_wgrad_partial<1, BF, PIPE>, launch_wgrad_partial<2, BF, PIPE>, launch_wgrad_partial<4, BF, PIPE>, launch_wgrad_partial<8, BF, PIPE>}
+void (*const PARTIAL_FN[2][2][4])(const WgradLaunch&, const WgradArgs&) = {{PARTIAL_NT(false, false), PARTIAL_NT(false, true)},
+                                                                          {PARTIAL_NT(true, false), PARTIAL_NT(true, true)}};   // [bf16][pipe][log2 NT]
+#undef PARTIAL_NT
+
+// ---- the walks ----
+WgradWalk wgrad_walk(const WgradCall& c, int swap, int rows) { return {swap, rows, swap ? c.Cout : c.Cin, swap ? c.Cin : c.Cout}; }
+
+// the walk of the row-stationary families: the smaller side of the rulebook where the input side is under half the output side
+WgradWalk wgrad_short_walk(const WgradCall& c) {
+  const int swap = c.n_in > 0 && 2LL * c.n_in < c.n_out;
+  return wgrad_walk(c, swap, swap ? c.n_in : c.n_out);
+}
+
+// an operand of `rows` rows x C elements of esz bytes that a kernel reaches through 32-bit byte offsets (4 GB)
+bool wgrad_fits32(long long rows, long long C, long long esz) { return rows * C * esz < 0xFFFFFF00LL; }
+
+// ---- per-family plans: false = the family does not take this shape; true = *L describes its launch ----
+
+// row-stationary kernels: supported (MT, NT) tile shapes and enough rows to amortise the persistent walk
+bool wgrad_plan_rows(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
+  const int mt = btc_cdiv(w.Cg, 16), nt = btc_cdiv(w.Cc, 16);
+  int tile = -1;
+  for (int i = 0; i < N_ROWS_TILES; ++i)
+    if (ROWS_TILES[i].mt == mt && ROWS_TILES[i].nt == nt) tile = i;
+  if (tile < 0 || w.rows < 4096 || c.K > 64) return false;
+  // Work split (tools/conv_bench.py, MI355X): two workgroups per CU (512 in all) = row splits x offset groups.  More
+  // phases per group = fewer groups re-reading the dOut tile but a larger accumulator slab per workgroup (PH = 7 no
+  // longer fits two workgroups per CU) and more slab traffic; the largest PH <= 4 that still leaves >= 3 row tiles
+  // per workgroup measured best from 12 K to 210 K rows (e.g. 32->32 at 210 K rows 307 -> 219 us, at 12 K rows 63 -> 30 us).
+  const int t_ph = btc_tune_get(BTC_TUNE_WGRAD_PH), t_wgs = btc_tune_get(BTC_TUNE_WGRAD_WGS);
+  // software-pipelined variant (conv_wgrad_rows_p) when the gathered operand's channel count is a multiple of 4
+  const bool pipe = (w.Cg & (bf ? 7 : 3)) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1;   // bf16: 8-channel gathers
+  const int wgs = t_wgs ? t_wgs : 512;
+  const int n_tiles = btc_cdiv(w.rows, TM);
+  const RowsTile& t = pipe ? ROWS_P_TILES[tile] : ROWS_TILES[tile];
+  int ph = t.ph;
+  if (pipe) {
+    // few tiles: half the phases per workgroup = twice the offset groups = twice the workgroups
+    if ((long long)n_tiles * btc_cdiv(c.K, t.kb * ph) < 3LL * wgs) ph >>= 1;
+    if (t_ph == ph * 2 || t_ph * 2 == ph) ph = t_ph;   // tuning runs: the other variant
+    L->fn = t.fn[bf][ph == t.ph ? 0 : 1];
+    // As[2][KB][TM][LDA] | s_nbr[3][TM][KB * PH] | s_row[3][TM]
+    L->lds = (size_t)(2 * t.kb * TM * ldb_of(mt)) * sizeof(float) + (size_t)(3 * TM * t.kb * ph + 3 * TM) * sizeof(int32_t);
+  } else {
+    if (!ph) {
+      ph = 1;
+      for (int cand = 4; cand > 1; cand >>= 1)
+        if ((long long)n_tiles * btc_cdiv(c.K, t.kb * cand) >= 3LL * wgs) { ph = cand; break; }
+      if (t_ph) ph = t_ph;
+    }
+    L->fn = t.fn[bf][ph == 1 ? 0 : (ph == 2 ? 1 : (ph == 4 ? 2 : 3))];
+    // As[KB][TM][LDA] | Ds[TM][LDB] | s_nbr[TM][K] | s_kact[K] | s_row[TM]
+    L->lds = (size_t)(t.kb * TM * ldb_of(mt) + TM * ldb_of(nt)) * sizeof(float) + (size_t)(TM * c.K + c.K + TM) * sizeof(int32_t);
+  }
+  L->family = pipe ? WG_ROWS_P : WG_ROWS;
+  L->walk = w;
+  L->groups = btc_cdiv(c.K, t.kb * ph);
+  int S = wgs / L->groups;
+  if (S > n_tiles / 2) S = n_tiles / 2;  // at least two row tiles per persistent workgroup
+  if (S > n_tiles) S = n_tiles;
+  L->S = S < 1 ? 1 : S;
+  return true;
+}
+
+// offset-major kernels: everything else, over the output rows
+void wgrad_plan_partial(bool bf, const WgradCall& c, WgradLaunch* L) {
+  const bool pipe = ((c.Cin | c.Cout) & 3) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1;
+  const int lnt = c.Cout <= 16 ? 0 : (c.Cout <= 32 ? 1 : (c.Cout <= 64 ? 2 : 3)), nt = 1 << lnt;
+  L->family = pipe ? WG_PARTIAL_P : WG_PARTIAL;
+  L->walk = wgrad_walk(c, 0, c.n_out);
+  L->fn = PARTIAL_FN[bf][pipe][lnt];
+  L->lds = (size_t)(TM * WG_LDA + TM * ldb_of(nt)) * sizeof(float) + (4 * TM + 2) * sizeof(int32_t);
+  L->n_cblk = btc_cdiv(c.Cout, nt * 16);
+  L->n_mblk = btc_cdiv(c.Cin, 64);
+  const int n_tiles = btc_cdiv(c.n_out > 0 ? c.n_out : 1, TM);
+  int S = 1536 / (c.K * L->n_cblk * L->n_mblk);
+  if (S > 32) S = 32;
+  if (S < 1) S = 1;
+  if (S > n_tiles) S = n_tiles;
+  L->tiles_per_split = btc_cdiv(n_tiles, S);
+  L->S = btc_cdiv(n_tiles, L->tiles_per_split);
+}
+
+// the row-stationary walk on the bf16 matrix pipe (conv_wgrad_x.hip): bf16 activations as they are, fp32 activations as three exact
+// bf16 pieces; any channel counts whose gathered side is a multiple of 16 (a workgroup owns a <= 64 x 64 block of every dW[k])
+bool wgrad_plan_x(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
+  const int mode = bf ? 0 : 1;
+  if (w.rows < 2048 || !btc_wgrad_x_supported(mode, c.K, w.Cg, w.Cc)) return false;
+  int ph;
+  L->family = WG_X;
+  L->walk = w;
+  btc_wgrad_x_plan(mode, w.rows, c.K, w.Cg, w.Cc, &L->S, &ph);
+  return true;
+}
+
+// narrow layers on the fp32 matrix pipe (conv_wgrad_n.hip): kind 1, a narrow RESULT (the 5-channel occupancy head), walks the layer's
+// INPUT rows -- x read once, dy gathered; kind 2, a narrow INPUT (the 4- / 6-channel first layers), walks the OUTPUT rows -- dOut read
+// once, the features gathered through nbr_out
+bool wgrad_plan_n(const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
+  if (btc_wgrad_n_kind(c.K, c.Cin, c.Cout) != (w.swap ? 1 : 2)) return false;
+  L->family = WG_N;
+  L->walk = w;
+  L->S = btc_wgrad_n_plan(w.rows);
+  return true;
+}
+
+// the most slabs any launch of this call can write: every family that takes the shape, for both activation types and both walk sides --
+// whatever BTC_TUNE_WGRAD_X, _NARROW and BTC_TUNE_SPLIT say and whatever the 4 GB bounds allow, so that a switch flipped between sizing and
+// launch cannot leave the buffer short (the keys that shape a split, _WGS, _PH, _PIPE, enter here as they enter the launch)
+int wgrad_max_slabs(const WgradCall& c) {
+  const WgradWalk out = wgrad_walk(c, 0, c.n_out), w = wgrad_short_walk(c);
+  WgradLaunch L = {};
+  int S = 1;
+  for (int bf = 0; bf < 2; ++bf) {
+    // (the bf16 instances of the pipelined kernel want 8-channel gathers, so the two plans can differ)
+    if (!wgrad_plan_rows(bf, c, w, &L)) wgrad_plan_partial(bf, c, &L);
+    if (L.S > S) S = L.S;
+    if (wgrad_plan_x(bf, c, out, &L) && L.S > S) S = L.S;
+    if (w.swap && wgrad_plan_x(bf, c, w, &L) && L.S > S) S = L.S;
+  }
+  // narrow layers: either walk side at either row count (kind 1 walks n_out rows where the map is mirrored)
+  for (int swap = 0; swap < 2; ++swap) {
+    if (wgrad_plan_n(c, wgrad_walk(c, swap, c.n_out), &L) && L.S > S) S = L.S;
+    if (c.n_in > 0 && wgrad_plan_n(c, wgrad_walk(c, swap, c.n_in), &L) && L.S > S) S = L.S;
+  }
+  return S;
+}
+
+// the launch of one call: the first family, in this order, that takes the shape and that the tuning keys and the 4 GB bounds allow
+WgradLaunch wgrad_choose(bool bf, const WgradCall& c) {
+  WgradLaunch L = {};
+  // the n and x families gather through 32-bit byte offsets: both operands under 4 GB, so the row count of `feat` must be known
+  const long long esz = bf ? 2 : 4;
+  const bool fits = c.n_feat >= 0 && wgrad_fits32(c.n_feat, c.Cin, esz) && wgrad_fits32(c.n_out, c.Cout, esz);
+  if (btc_tune_get(BTC_TUNE_WGRAD_NARROW) != 1) {
+    // (n reaches its map through 32-bit offsets as well)
+    const WgradWalk in = wgrad_walk(c, 1, c.mirror ? c.n_out : c.n_in), out = wgrad_walk(c, 0, c.n_out);
+    if ((c.mirror || c.n_in >= 0) && in.rows >= 2048 && fits && wgrad_fits32(in.rows, c.K, 4) && wgrad_plan_n(c, in, &L)) return L;
+    // (not where the rulebook's input side is less than half the output side: the kernels below walk that side -- 4 -> 16 from 8.4 K to
+    // 40 K rows: 13.6 us there, 23.8 here)
+    if (!(c.n_in >= 0 && 2LL * c.n_in < c.n_out) && out.rows >= 2048 && fits && wgrad_fits32(out.rows, c.K, 4) && wgrad_plan_n(c, out, &L)) return L;
+  }
+  const WgradWalk w = wgrad_short_walk(c);
+  if (btc_tune_get(BTC_TUNE_WGRAD_X) != 1 && (bf || btc_tune_get(BTC_TUNE_SPLIT) != 1) && fits && wgrad_plan_x(bf, c, w, &L)) return L;
+  if (!wgrad_plan_rows(bf, c, w, &L)) wgrad_plan_partial(bf, c, &L);
+  return L;
+}
+
+// every family ends the same way
+int wgrad_finish(const float* part, int S, long long count, float* dW, int* slabs_out, hipStream_t stream) {
+  BTC_LAUNCH_CHECK();
+  if (slabs_out) {
+    *slabs_out = S;
+    return BTC_OK;
+  }
+  wgrad_reduce<<<btc_cdiv(count, 256), 256, 0, stream>>>(part, S, count, dW);
+  BTC_LAUNCH_CHECK();
+  return BTC_OK;
+}
+
+int wgrad_impl(bool bf, const void* feat_, const void* dout_, const int32_t* nbr_out, int n_out, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
+               float* dW, void* ws, size_t ws_bytes, void* stream_, const int32_t* order_out = nullptr, const int32_t* order_in = nullptr,
+               int* slabs_out = nullptr) {
+  // slabs_out: the caller adds the slabs up itself, later (btc_wgrad_reduce_multi): *slabs_out = S > 0 slabs of K Cin Cout floats
+  // in `ws`, dW untouched -- or 0: dW is complete (no rows: zeros)
+  hipStream_t stream = (hipStream_t)stream_;
+  const float *feat = (const float*)feat_, *dout = (const float*)dout_;
+  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_wgrad: bad sizes");
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_wgrad: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
+  // rows of `feat`: n_in when the backward map comes with it, or when a caller without one states a positive count; a legacy call that
+  // passes NULL and 0 (the argument used to be ignored without a map) leaves it unknown -> the fp32-pipe kernels, which need no bound
+  // nbr_in == nbr_out (the same pointer, n_in == n_out): a submanifold layer -- its backward map is the forward map with the offset index
+  // mirrored, nothing else is stored (rulebook.hip); the kernels that walk the output rows take it as "no backward map"
+  WgradCall c = {n_out, K, Cin, Cout, n_in, n_in, nbr_in != nullptr && nbr_in == nbr_out && n_in == n_out};
+  const bool have_bwd = nbr_in != nullptr && !c.mirror;
+  if (!have_bwd && n_in <= 0) c.n_feat = -1;
+  if (!have_bwd) c.n_in = -1;
+  BTC_CHECK_ARG(ws_bytes >= btc_conv_wgrad_ws_bytes(n_out, K, Cin, Cout, c.n_in), "btc_conv_wgrad: workspace too small");
+  const long long count = (long long)K * Cin * Cout;
+  if (slabs_out) *slabs_out = 0;
+  if (n_out <= 0) {
+    BTC_HIP(hipMemsetAsync(dW, 0, (size_t)count * sizeof(float), stream));
+    return BTC_OK;
+  }
+  const WgradLaunch L = wgrad_choose(bf, c);
+  BTC_CHECK_ARG((size_t)L.S * count * sizeof(float) <= ws_bytes, "btc_conv_wgrad: the chosen kernel (family %d) writes %d slabs, more than the workspace holds",
+                (int)L.family, L.S);
+  const int swap = L.walk.swap;
+  const WgradArgs a = {swap ? dout : feat, swap ? feat : dout, swap && !c.mirror ? nbr_in : nbr_out, swap ? order_in : order_out, K, (float*)ws, stream};
+  int rc = BTC_OK;
+  if (L.family == WG_N)   // flags: 1 mirrored map, 2 narrow input
+    rc = btc_launch_wgrad_n(bf, a.c, a.g, a.map, L.walk.rows, K, L.walk.Cc, L.walk.Cg, a.part, swap ? (c.mirror ? 1 : 0) : 2, stream);
+  else if (L.family == WG_X)
+    rc = btc_launch_wgrad_x(bf ? 0 : 1, a.g, a.c, a.map, a.ord, L.walk.rows, K, L.walk.Cg, L.walk.Cc, a.part, swap, stream);
+  else
+    L.fn(L, a);
+  if (rc != BTC_OK) return rc;
+  return wgrad_finish(a.part, L.S, count, dW, slabs_out, stream);
+}
+
+}  // namespace
+
+extern "C" size_t btc_conv_wgrad_ws_bytes(int n_out, int K, int Cin, int Cout, int n_in) {
+  const WgradCall c = {n_out, K, Cin, Cout, n_in, n_in, false};
+  return btc_align((size_t)wgrad_max_slabs(c) * K * Cin * Cout * sizeof(float));
+}
+
+extern "C" int btc_conv_wgrad(const float* feat, const float* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
+                              int n_in, int K, int Cin, int Cout, float* dW, void* ws, size_t ws_bytes, void* stream) {
+  return wgrad_impl(false, feat, dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream);
+}
+
+extern "C" int btc_conv_wgrad_bf16(const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
+                                   int n_in, int K, int Cin, int Cout, float* dW, void* ws, size_t ws_bytes, void* stream) {
+  return wgrad_impl(true, feat, dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream);
+}
+
+extern "C" int btc_conv_wgrad_ordered(int bf16_act, const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
+                                      int n_in, const int32_t* order_out, const int32_t* order_in, int K, int Cin, int Cout, float* dW, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  return wgrad_impl(bf16_act != 0, feat, dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out, order_in);
+}
+
+extern "C" int btc_conv_wgrad_slabs(int bf16_act, const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
+                                    int n_in, const int32_t* order_out, const int32_t* order_in, int K, int Cin, int Cout, float* dW, void* ws,
+                                    size_t ws_bytes, int* n_slabs, void* stream) {
+  BTC_CHECK_ARG(n_slabs != nullptr, "btc_conv_wgrad_slabs: n_slabs is NULL");
+  return wgrad_impl(bf16_act != 0, feat, dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out, order_in, n_slabs);
+}
+
+extern "C" int btc_wgrad_reduce_multi(const float* const* parts, float* const* dWs, const int* n_slabs, const long long* counts, int n_jobs,
+                                      void* stream) {
+  BTC_CHECK_ARG(n_jobs >= 0 && (n_jobs == 0 || (parts && dWs && n_slabs && counts)), "btc_wgrad_reduce_multi: bad arguments");
+  for (int base = 0; base < n_jobs; base += BTC_WGRAD_MULTI_MAX) {
+    ReduceJobs jobs;
+    jobs.n = n_jobs - base < BTC_WGRAD_MULTI_MAX ? n_jobs - base : BTC_WGRAD_MULTI_MAX;
+    long long blocks = 0;
+    for (int j = 0; j < jobs.n; ++j) {
+      BTC_CHECK_ARG(n_slabs[base + j] >= 1 && counts[base + j] >= 1 && parts[base + j] && dWs[base + j], "btc_wgrad_reduce_multi: bad job %d", base + j);
+      jobs.part[j] = parts[base + j];
+      jobs.dW[j] = dWs[base + j];
+      jobs.S[j] = n_slabs[base + j];
+      jobs.count[j] = counts[base + j];
+      jobs.block0[j] = (int)blocks;
+      blocks += (counts[base + j] + 255) / 256;
+    }
+    jobs.block0[jobs.n] = (int)blocks;
+    BTC_CHECK_ARG(blocks < (1LL << 31), "btc_wgrad_reduce_multi: too many elements");
+    wgrad_reduce_multi<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(jobs);
+    BTC_LAUNCH_CHECK();
+  }
+  return BTC_OK;
+}

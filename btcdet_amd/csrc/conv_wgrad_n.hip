@@ -22,8 +22,6 @@
 // one slab per workgroup, slabs added in index order by wgrad_reduce / btc_wgrad_reduce_multi: deterministic.
 #include "btc_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int NTL_MAX = 11;                 // 16-column tiles of the (k', narrow channel) dimension: 9 (K Cn <= 144) or 11 (<= 176) per instance
@@ -177,7 +175,6 @@ int btc_wgrad_n_kind(int K, int Cin, int Cout) {
   if (Cin <= 8 && K * Cin <= 16 * NTL_MAX && Cout >= 16 && (Cout & 15) == 0) return 2;
   return 0;
 }
-bool btc_wgrad_n_supported(int K, int Cin, int Cout) { return btc_wgrad_n_kind(K, Cin, Cout) == 1; }
 
 // slabs (= workgroups along x) of a launch over `rows` walked rows
 int btc_wgrad_n_plan(int rows) {

@@ -3,7 +3,7 @@
 //     dW[k][ci][co] = sum_rows  g[nbr[row][k]][ci] * c[row][co]
 //
 // is a contraction over ROWS: for `v_mfma_f32_16x16x32_bf16` both operands must hold 8 consecutive reduction indices -- 8 rows of ONE
-// channel -- per lane, while the activations are stored row-major (a row's channels are contiguous).  conv_wgrad_rows_p (sparse_conv.hip)
+// channel -- per lane, while the activations are stored row-major (a row's channels are contiguous).  conv_wgrad_rows_p (conv_wgrad.hip)
 // sidesteps that with `v_mfma_f32_16x16x4_f32`, whose operands are one value per lane, at 32 cycles of the matrix pipe per 4 rows; this
 // kernel keeps the row-major image in LDS and reads the gathered operand with gfx950's transposing LDS read (`ds_read_b64_tr_b16`: a
 // 16-lane group reads a 4-row x 16-channel block, lane t comes back with column t), two reads per 32-row step:
@@ -26,7 +26,6 @@
 
 #include "btc_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));

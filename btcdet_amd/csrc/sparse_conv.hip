@@ -10,20 +10,17 @@
 //
 // Roofline: HBM/L2 bound at BtcDet's channel widths: per output row the kernel
 // moves (pairs * Cin + Cout) * 4 B and does 2 * pairs * Cin * Cout flop.
+//
+// Forward, data gradient, max-pool and to-dense live here; the weight gradient is in conv_wgrad.hip.
 #include <mutex>
 
 #include "btc_common.h"
 #include "bn_fuse.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int TM = 64;       // output rows per workgroup
 constexpr int KC = 32;       // reduction-channel chunk staged in LDS
 constexpr int LDA = KC + 2;  // bank-conflict-free A fragment reads (ds_read_b32, 2 x 32-lane groups)
-
-__host__ __device__ constexpr int ldb_of(int nt) { return nt * 16 + (((nt * 16) % 32 == 0) ? 16 : 0); }
 
 // out[i] = bias + sum_k feat[nbr[i][k]] @ Wk     (TRANS_W = false: Wk = W[k]      (Cin x Cout), fwd)
 // din[j] =        sum_k dout[nbr[j][k]] @ Wk     (TRANS_W = true : Wk = W[k]^T    (Cout x Cin), dgrad)
@@ -350,670 +347,6 @@ __global__ __launch_bounds__(WS_WAVES * 64) void conv_apply_ws(const float* __re
   if (bn.slots) bn_fuse_finish(bn, (int*)smem, (double*)(smem + 16));
 }
 
-// dW partial: part[s][k][ci][co] = sum over the split's rows of feat[nbr[i][k]][ci] * dout[i][co]
-// block = (k, split, tile of 64 Cin x NT*16 Cout); wave w owns dW rows [m0 + 16w, m0 + 16w + 16)
-constexpr int WG_LDA = 64 + 16;
-template <int NT, bool BF>
-__global__ __launch_bounds__(256) void conv_wgrad_partial(const float* __restrict__ feat, const float* __restrict__ dout,
-                                                          const int32_t* __restrict__ nbr, int n_out, int K, int Cin,
-                                                          int Cout, int tiles_per_split, int n_cblk, float* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int LDB = ldb_of(NT);
-  float* As = (float*)smem;       // [TM][WG_LDA]  gathered input rows, 64 channels
-  float* Ds = As + TM * WG_LDA;   // [TM][LDB]     dout rows, NT*16 channels
-  int32_t* s_j = (int32_t*)(Ds + TM * LDB);  // [TM] (kept inside the one dynamic LDS array)
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x, split = blockIdx.y;
-  const int m0 = (blockIdx.z / n_cblk) * 64;
-  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int t_begin = split * tiles_per_split;
-  const int t_end = min(n_tiles, t_begin + tiles_per_split);
-
-  f32x4 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int kq = lane >> 4;
-  const bool wave_live = (m0 + wave * 16) < Cin;
-
-  for (int t = t_begin; t < t_end; ++t) {
-    const int row0 = t * TM;
-    int j = -1;
-    if (tid < TM && row0 + tid < n_out) j = nbr[(size_t)(row0 + tid) * K + k];
-    if (tid < TM) s_j[tid] = j;
-    if (!__syncthreads_or(j >= 0)) continue;
-    // all loads of a thread are issued before the first LDS store (one memory latency per tile)
-    if (((Cin | Cout) & 3) == 0) {
-      float4 va[4], vd[NT];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-        int jj = s_j[r];
-        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c)
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-        float* d = As + r * WG_LDA + c;
-        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        float* d = Ds + r * LDB + c;
-        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
-      }
-    } else {
-      float va[16], vd[NT * 4];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        int e = i * 256 + tid, r = e >> 6, c = e & 63;
-        int jj = s_j[r];
-        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld1<BF>(feat, (size_t)jj * Cin + m0 + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld1<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        int e = i * 256 + tid, r = e >> 6, c = e & 63;
-        As[r * WG_LDA + c] = va[i];
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        Ds[r * LDB + c] = vd[i];
-      }
-    }
-    __syncthreads();
-    if (wave_live) {
-#pragma unroll 4
-      for (int q = 0; q < TM / 4; ++q) {
-        float a = As[(q * 4 + kq) * WG_LDA + wave * 16 + (lane & 15)];
-        const float* bp = Ds + (q * 4 + kq) * LDB + (lane & 15);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[nt * 16], acc[nt], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  float* P = part + ((size_t)split * K + k) * Cin * Cout;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + nt * 16 + (lane & 15);
-    if (col >= Cout) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ci = m0 + wave * 16 + kq * 4 + r;
-      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
-    }
-  }
-}
-
-// conv_wgrad_partial for channel counts that are multiples of 4, with
-//  * the next tile's loads in flight during this tile's MFMAs: the map column entry of tile t + 1 is read while tile t is being
-//    staged, its gathered rows and dOut rows are requested right after tile t's tiles are visible in LDS and sit in registers
-//    until tile t's MFMAs are done (same LDS footprint, same two barriers per tile);
-//  * per-tile packing: only the rows of the tile that HAVE the offset are staged, packed to the front of the LDS tiles (a wave
-//    ballot over the column gives every live row its slot), and the reduction runs over ceil(m / 4) 4-row steps instead of 16.
-//    Both operands are gathered per offset here anyway, so packing costs no indirection in the MFMA loop.  At the wide layers
-//    that land on this kernel (128 -> 128, 256 -> 128 on the 8x-downsampled level) 55 % of the (row, offset) slots are live.
-// Skipped terms are exact zeros; dW differs from the unpacked sum only in how rows group into 4-row MFMA steps.
-template <int NT, bool BF>
-__global__ __launch_bounds__(256) void conv_wgrad_partial_p(const float* __restrict__ feat, const float* __restrict__ dout,
-                                                            const int32_t* __restrict__ nbr, int n_out, int K, int Cin, int Cout,
-                                                            int tiles_per_split, int n_cblk, float* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int LDB = ldb_of(NT);
-  float* As = (float*)smem;       // [TM][WG_LDA]  gathered input rows (packed), 64 channels
-  float* Ds = As + TM * WG_LDA;   // [TM][LDB]     dout rows (packed), NT*16 channels
-  int32_t* s_src = (int32_t*)(Ds + TM * LDB);  // [2][TM] input row of packed slot t (-1: padding of the last 4-row step)
-  int32_t* s_dst = s_src + 2 * TM;             // [2][TM] output row of packed slot t
-  int32_t* s_m = s_dst + 2 * TM;               // [2] live rows of the tile
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x, split = blockIdx.y;
-  const int m0 = (blockIdx.z / n_cblk) * 64;
-  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int t_begin = split * tiles_per_split;
-  const int t_end = min(n_tiles, t_begin + tiles_per_split);
-
-  f32x4 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int kq = lane >> 4;
-  const bool wave_live = (m0 + wave * 16) < Cin;
-
-  float4 va[4], vd[NT];
-  auto load_j = [&](int t) {   // wave 0: map column entry of row `lane` of tile t
-    const int row = t * TM + lane;
-    return (wave == 0 && t < t_end && row < n_out) ? nbr[(size_t)row * K + k] : -1;
-  };
-  auto pack = [&](int t, int j, int b) {   // wave 0: packed slots of tile t into buffer b
-    if (wave != 0) return;
-    const unsigned long long live = __ballot(j >= 0);
-    const int m = __popcll(live);
-    if (j >= 0) {
-      const int slot = __popcll(live & ((1ull << lane) - 1ull));
-      s_src[b * TM + slot] = j;
-      s_dst[b * TM + slot] = t * TM + lane;
-    }
-    if (lane >= m && lane < ((m + 3) & ~3)) {
-      s_src[b * TM + lane] = -1;
-      s_dst[b * TM + lane] = -1;
-    }
-    if (lane == 0) s_m[b] = m;
-  };
-  auto load_tile = [&](int b) {
-    const int m4 = (s_m[b] + 3) & ~3;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-      const int jj = r < m4 ? s_src[b * TM + r] : -1;
-      va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-      const int ro = r < m4 ? s_dst[b * TM + r] : -1;
-      vd[i] = (ro >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)ro * Cout + n0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto store_tile = [&](int m4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-      if (r < m4) {
-        float* d = As + r * WG_LDA + c;
-        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-      if (r < m4) {
-        float* d = Ds + r * LDB + c;
-        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
-      }
-    }
-  };
-
-  // prologue: the first tile's column and loads, the second tile's column
-  int m4 = 0, jn = -1;
-  if (t_begin < t_end) {
-    pack(t_begin, load_j(t_begin), 0);
-    __syncthreads();
-    m4 = (s_m[0] + 3) & ~3;
-    if (m4) load_tile(0);
-    jn = load_j(t_begin + 1);
-  }
-  for (int t = t_begin; t < t_end; ++t) {
-    const int cur = (t - t_begin) & 1;
-    if (m4) store_tile(m4);            // tile t: registers -> LDS (the previous tile's MFMAs ended at the barrier below)
-    pack(t + 1, jn, cur ^ 1);          // tile t + 1's packed slots
-    __syncthreads();                   // tile t in LDS; everyone sees tile t + 1's slots
-    const int m4_next = (s_m[cur ^ 1] + 3) & ~3;
-    if (m4_next) load_tile(cur ^ 1);   // in flight during the MFMAs below
-    jn = load_j(t + 2);
-    if (m4 && wave_live) {
-      const int steps = m4 >> 2;
-      const float* ap = As + kq * WG_LDA + wave * 16 + (lane & 15);
-      const float* bp = Ds + kq * LDB + (lane & 15);
-#pragma unroll 4
-      for (int q = 0; q < steps; ++q) {
-        const float a = ap[q * 4 * WG_LDA];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[q * 4 * LDB + nt * 16], acc[nt], 0, 0, 0);
-      }
-    }
-    __syncthreads();   // MFMAs of tile t done: the LDS tiles may be overwritten
-    m4 = m4_next;
-  }
-  float* P = part + ((size_t)split * K + k) * Cin * Cout;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + nt * 16 + (lane & 15);
-    if (col >= Cout) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ci = m0 + wave * 16 + kq * 4 + r;
-      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Row-stationary weight gradient for the large-N / small-C layers (the occupancy branch: up to 210 K rows at 32
-// channels).  A persistent workgroup walks row tiles; per tile the dOut rows and the neighbour-map rows are loaded
-// ONCE (coalesced, row-major) and the K offsets are processed in phases of KB gathered input tiles; the whole
-// dW slab of the workgroup's offset group (PH*KB offsets x Cin x Cout) lives in MFMA accumulators for the entire
-// walk and is written out once.  (The offset-major kernel below re-reads dOut K times and reads the map column-wise.)
-//   MT, NT : 16-wide tiles of Cin / Cout;  KB : offsets per LDS phase;  PH : phases per offset group
-// ------------------------------------------------------------------------------------------------------------
-template <int MT, int NT, int KB, int PH, bool BF>
-__global__ __launch_bounds__(256) void conv_wgrad_rows(const float* __restrict__ feat, const float* __restrict__ dout,
-                                                       const int32_t* __restrict__ nbr, const int32_t* __restrict__ order, int n_out, int K,
-                                                       int Cin, int Cout, float* __restrict__ part, int swap, int dbg) {
-  // order (optional, row_order.hip): tile slot t works on map row order[t]; rows with the same offsets share tiles, so fewer
-  // offset phases per tile are live.  dW is the fp32 sum over rows in walk order.
-  // Naming follows the un-swapped case: `feat` = gathered operand (Cin channels, via the map), `dout` = contiguous
-  // operand (Cout channels), one tile per 64 map rows.  swap = 1: the walk is over the INPUT rows instead (map =
-  // nbr_in, gathered = dOut, contiguous = features) -- used when the layer has far fewer input than output rows
-  // (transposed / dilating convs) -- and the slab is written transposed so that dW keeps the [K][Cin][Cout] layout.
-  constexpr int TPP = KB * MT * NT / 4;  // accumulator tiles per wave per phase
-  static_assert(KB * MT * NT % 4 == 0, "phase tiles must split evenly over the 4 waves");
-  constexpr int LDA = ldb_of(MT), LDB = ldb_of(NT);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* As = (float*)smem;                       // [KB][TM][LDA]
-  float* Ds = As + KB * TM * LDA;                 // [TM][LDB]
-  int32_t* s_nbr = (int32_t*)(Ds + TM * LDB);     // [TM][K]
-  int32_t* s_kact = s_nbr + TM * K;               // [K]
-  int32_t* s_row = s_kact + K;                    // [TM] map row of each tile slot, -1 past the end
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
-  const int kg0 = blockIdx.y * (PH * KB);         // first offset of this workgroup's group
-  const int n_tiles = (n_out + TM - 1) / TM;
-
-  f32x4 acc[PH * TPP];
-#pragma unroll
-  for (int t = 0; t < PH * TPP; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int row0 = tile * TM;
-    for (int e = tid; e < K; e += 256) s_kact[e] = 0;
-    if (tid < TM) s_row[tid] = (row0 + tid < n_out) ? (order ? order[row0 + tid] : row0 + tid) : -1;
-    __syncthreads();
-    for (int e = tid; e < TM * K; e += 256) {
-      const int rloc = e / K, kk = e - rloc * K;
-      const int gr = s_row[rloc];
-      const int v = gr >= 0 ? nbr[(long long)gr * K + kk] : -1;
-      s_nbr[e] = v;
-      if (v >= 0) s_kact[kk] = 1;
-    }
-    // dOut tile: all loads of a thread are issued before the first LDS store (one latency, not one per element)
-    if ((Cout & 3) == 0) {
-      float4 v[NT];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        const int gr = s_row[r];
-        v[i] = (gr >= 0 && c < Cout) ? btc_ld4<BF>(dout, (size_t)gr * Cout + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        float* d = Ds + r * LDB + c;
-        d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-      }
-    } else {
-      float v[NT * 4];
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        const int gr = s_row[r];
-        v[i] = (gr >= 0 && c < Cout) ? btc_ld1<BF>(dout, (size_t)gr * Cout + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        Ds[r * LDB + c] = v[i];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < PH; ++p) {
-      const int k0 = kg0 + p * KB;
-      int any = 0;
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) any |= (k0 + kb < K) ? s_kact[k0 + kb] : 0;
-      if (!any) continue;  // block-uniform
-      // gather KB input tiles; loads batched in registers as above
-      if ((Cin & 3) == 0) {
-        float4 v[KB * MT];
-#pragma unroll
-        for (int i = 0; i < KB * MT; ++i) {
-          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
-          if (dbg & 8) j = -1;  // timing experiments only (BTC_TUNE_APPLY_DEBUG, tools/wgrad_bench.py): no gathers
-          v[i] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < KB * MT; ++i) {
-          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-          float* d = As + (kb * TM + r) * LDA + c;
-          d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-        }
-      } else {
-        float v[KB * MT * 4];
-#pragma unroll
-        for (int i = 0; i < KB * MT * 4; ++i) {
-          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
-          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
-          v[i] = (j >= 0 && c < Cin) ? btc_ld1<BF>(feat, (size_t)j * Cin + c) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < KB * MT * 4; ++i) {
-          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
-          As[(kb * TM + r) * LDA + c] = v[i];
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < TPP; ++q) {
-        if (dbg & 4) continue;       // timing experiments only: no MFMA phase
-        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt)
-        const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-        const float* ap = As + (size_t)kb * TM * LDA + mt * 16 + (lane & 15);
-        const float* bp = Ds + nt * 16 + (lane & 15);
-        f32x4 a4 = acc[p * TPP + q];
-#pragma unroll 4
-        for (int s = 0; s < TM / 4; ++s)
-          a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[(s * 4 + kq) * LDA], bp[(s * 4 + kq) * LDB], a4, 0, 0, 0);
-        acc[p * TPP + q] = a4;
-      }
-      __syncthreads();
-    }
-  }
-  // write this workgroup's slab: part[blockIdx.x][k][ci][co]
-  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
-#pragma unroll
-  for (int p = 0; p < PH; ++p)
-#pragma unroll
-    for (int q = 0; q < TPP; ++q) {
-      const int l = q * 4 + wave;
-      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-      const int k = kg0 + p * KB + kb;
-      const int co = nt * 16 + (lane & 15);
-      if (k >= K || co >= Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int ci = mt * 16 + kq * 4 + r;
-        if (ci < Cin) {
-          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
-          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];  // here ci indexes dOut channels, co feature channels
-        }
-      }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// conv_wgrad_rows, software-pipelined (gathered-operand channel counts that are multiples of 4).  tools/wgrad_bench.py on the
-// kernel above: removing the MFMA phase halves its time, removing the gathers changes nothing -- a workgroup alternates
-// between a staging round (issue the loads, wait one L2 / HBM latency, store to LDS, barrier: ~1.8 us) and an MFMA phase of
-// about the same length, and only the other workgroup of the CU fills the holes.  Here
-//  * the loads of item g + 1 (the gathered rows of the next phase; the map rows of the tile after next) are issued right
-//    after item g's barrier and land in registers while item g's MFMAs run; they are stored to the OTHER LDS buffer at the
-//    top of item g + 1: one barrier per item, no exposed load latency;
-//  * the contiguous operand never goes through LDS: 4 % NT == 0, so a wave's accumulator tiles all share ONE 16-column block
-//    (nt = wave % NT), and its MFMA B fragments for the 16 4-row steps of a tile are 16 registers, loaded once per tile
-//    (prefetched during the previous tile's last phase) and reused by every offset of the group.  Half the LDS reads of the
-//    MFMA loop, and the LDS footprint drops to the double-buffered gather tile: 41-64 KB, two to three workgroups per CU.
-// Same tiles, same 4-row MFMA steps, same order over rows as the kernel above.  Items are all (tile, phase) pairs: a phase
-// none of whose offsets occurs in the tile costs zeros -- at 64-row tiles that is < 10 % of the phases of the layers this
-// kernel takes.
-//   LDS: As[2][KB][TM][LDA] | s_nbr[3][TM][NOFF] (the group's offsets only) | s_row[3][TM]
-// ------------------------------------------------------------------------------------------------------------
-template <int MT, int NT, int KB, int PH, bool BF>
-__global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict__ feat, const float* __restrict__ dout,
-                                                         const int32_t* __restrict__ nbr, const int32_t* __restrict__ order, int n_out, int K,
-                                                         int Cin, int Cout, float* __restrict__ part, int swap) {
-  constexpr int TPP = KB * MT * NT / 4;
-  static_assert(KB * MT * NT % 4 == 0, "phase tiles must split evenly over the 4 waves");
-  static_assert(4 % NT == 0, "a wave's tiles must share one column block");
-  constexpr int LDA = ldb_of(MT);
-  constexpr int NOFF = PH * KB;
-  constexpr int NV = (TM * NOFF + 255) / 256;   // map entries per thread and tile
-  constexpr int NS = TM / 4;                    // 4-row MFMA steps per tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* As = (float*)smem;                              // [2][KB][TM][LDA]
-  int32_t* s_nbr = (int32_t*)(As + 2 * KB * TM * LDA);   // [3][TM][NOFF]
-  int32_t* s_row = s_nbr + 3 * TM * NOFF;                // [3][TM]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
-  const int kg0 = blockIdx.y * NOFF;
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int nt_wg = ((int)blockIdx.x < n_tiles) ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;   // tiles of this workgroup
-  const int bcol = (wave % NT) * 16 + (lane & 15);   // this lane's column of the contiguous operand
-
-  f32x4 acc[PH * TPP];
-#pragma unroll
-  for (int t = 0; t < PH * TPP; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  int nv[NV], nrow = -1;            // the map rows (this group's offsets) and row ids of a tile, in flight
-  float4 gv[KB * MT];               // the gathered rows of an item, in flight
-  float bcur[NS], bnext[NS];        // B fragments of the tile / of the next tile (in flight)
-
-  auto load_map = [&](int i) {      // tile i of this workgroup -> registers
-    const int row0 = (blockIdx.x + i * gridDim.x) * TM;
-    if (tid < TM) nrow = (row0 + tid < n_out) ? (order ? order[row0 + tid] : row0 + tid) : -1;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = u * 256 + tid, r = e / NOFF, o = e - r * NOFF;
-      int v = -1;
-      if (e < TM * NOFF && row0 + r < n_out && kg0 + o < K) {
-        const int gr = order ? order[row0 + r] : row0 + r;
-        v = nbr[(long long)gr * K + kg0 + o];
-      }
-      nv[u] = v;
-    }
-  };
-  auto store_map = [&](int i) {
-    int32_t* dn = s_nbr + (i % 3) * TM * NOFF;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = u * 256 + tid;
-      if (e < TM * NOFF) dn[e] = nv[u];
-    }
-    if (tid < TM) s_row[(i % 3) * TM + tid] = nrow;
-  };
-  auto load_b = [&](int i) {        // B fragments of tile i (its row ids are in LDS): row 4 s + kq, column bcol
-    const int32_t* rows = s_row + (i % 3) * TM + kq;
-#pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) {
-      const int gr = rows[s2 * 4];
-      bnext[s2] = (gr >= 0 && bcol < Cout) ? btc_ld1<BF>(dout, (size_t)gr * Cout + bcol) : 0.f;
-    }
-  };
-  // bf16 activations (the launcher guarantees Cin % 8 == 0 for these instances): 16-byte loads of 8 channels -- half the load
-  // instructions of the 4-channel walk and half its staging registers (216 -> 152 VGPRs for the 64 x 64 shape: a third workgroup
-  // per CU) -- widened to fp32 on the way into LDS
-  constexpr int UPR8 = MT * 2;                             // 8-channel units per gathered row
-  constexpr int NU8 = BF ? (KB * TM * UPR8 + 255) / 256 : 1;   // units per thread and item
-  uint4 gq[NU8];
-  constexpr bool wide = BF;
-  auto load_g = [&](int i, int p) { // the gathered rows of phase p of tile i
-    const int32_t* mp = s_nbr + (i % 3) * TM * NOFF + p * KB;
-    if (wide) {
-#pragma unroll
-      for (int u = 0; u < NU8; ++u) {
-        const int e = u * 256 + tid, c8 = e % UPR8, r = (e / UPR8) % TM, kb = e / (UPR8 * TM);
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (e < KB * TM * UPR8) {
-          const int j = mp[r * NOFF + kb];
-          if (j >= 0 && c8 * 8 < Cin) v = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(feat) + (size_t)j * Cin + c8 * 8);
-        }
-        gq[u] = v;
-      }
-      return;
-    }
-#pragma unroll
-    for (int u = 0; u < KB * MT; ++u) {
-      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-      const int j = mp[r * NOFF + kb];
-      gv[u] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto store_g = [&](int buf) {
-    float* A = As + buf * KB * TM * LDA;
-    if (wide) {
-#pragma unroll
-      for (int u = 0; u < NU8; ++u) {
-        const int e = u * 256 + tid, c8 = e % UPR8, r = (e / UPR8) % TM, kb = e / (UPR8 * TM);
-        if (e < KB * TM * UPR8) {
-          float* d = A + (kb * TM + r) * LDA + c8 * 8;
-          const unsigned w[4] = {gq[u].x, gq[u].y, gq[u].z, gq[u].w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            d[2 * q] = __uint_as_float(w[q] << 16);
-            d[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-          }
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int u = 0; u < KB * MT; ++u) {
-      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-      float* d = A + (kb * TM + r) * LDA + c;
-      d[0] = gv[u].x; d[1] = gv[u].y; d[2] = gv[u].z; d[3] = gv[u].w;
-    }
-  };
-
-  if (nt_wg > 0) {
-    load_map(0);
-    store_map(0);
-    if (nt_wg > 1) {
-      load_map(1);
-      store_map(1);
-    }
-    __syncthreads();
-    load_b(0);
-    load_g(0, 0);
-  }
-  int buf = 0;
-  for (int i = 0; i < nt_wg; ++i) {
-#pragma unroll
-    for (int p = 0; p < PH; ++p) {
-      store_g(buf);
-      if (p == 0) {
-#pragma unroll
-        for (int s2 = 0; s2 < NS; ++s2) bcur[s2] = bnext[s2];
-      }
-      // the map rows that were loaded during the previous item: tile i + 2 (PH > 1: loaded at this tile's phase 0) or
-      // tile i + 1 (PH == 1: loaded during tile i - 1); tiles 0 and 1 come from the prologue
-      if (PH > 1 ? (p == 1 && i + 2 < nt_wg) : (i >= 1 && i + 1 < nt_wg)) store_map(PH > 1 ? i + 2 : i + 1);
-      __syncthreads();
-      // ---- loads for the next item, in flight during this item's MFMAs
-      if (p + 1 < PH) {
-        load_g(i, p + 1);
-      } else if (i + 1 < nt_wg) {
-        load_b(i + 1);
-        load_g(i + 1, 0);
-      }
-      if (PH > 1 ? (p == 0 && i + 2 < nt_wg) : (i + 2 < nt_wg)) load_map(i + 2);
-      // ---- MFMAs of item (i, p)
-      const float* A = As + buf * KB * TM * LDA;
-#pragma unroll
-      for (int q = 0; q < TPP; ++q) {
-        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt), nt == wave % NT
-        const int mt = (l / NT) % MT, kb = l / (NT * MT);
-        const float* ap = A + (size_t)kb * TM * LDA + mt * 16 + (lane & 15) + kq * LDA;
-        f32x4 a4 = acc[p * TPP + q];
-#pragma unroll
-        for (int s2 = 0; s2 < NS; ++s2) a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[s2 * 4 * LDA], bcur[s2], a4, 0, 0, 0);
-        acc[p * TPP + q] = a4;
-      }
-      buf ^= 1;
-    }
-  }
-  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
-#pragma unroll
-  for (int p = 0; p < PH; ++p)
-#pragma unroll
-    for (int q = 0; q < TPP; ++q) {
-      const int l = q * 4 + wave;
-      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-      const int k = kg0 + p * KB + kb;
-      const int co = nt * 16 + (lane & 15);
-      if (k >= K || co >= Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int ci = mt * 16 + kq * 4 + r;
-        if (ci < Cin) {
-          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
-          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];
-        }
-      }
-    }
-}
-
-// dW[e] = sum_s part[s][e] in slab order (deterministic); 8 loads in flight per thread
-__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ part, int S, long long count,
-                                                    float* __restrict__ dW) {
-  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= count) return;
-  float s = 0.f;
-  int q = 0;
-  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
-  // additions is the slab order either way)
-  for (; q + 16 <= S; q += 16) {
-    float v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) s += v[u];
-  }
-  for (; q + 8 <= S; q += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; q < S; ++q) s += part[(size_t)q * count + e];
-  dW[e] = s;
-}
-
-// the slab reductions of MANY layers in one launch (btc_wgrad_reduce_multi: every weight gradient of a backward pass whose dW nobody
-// reads before the side stream's join): block b works on job j with block0[j] <= b < block0[j + 1]; same sums, same order as wgrad_reduce
-struct ReduceJobs {
-  const float* part[BTC_WGRAD_MULTI_MAX];
-  float* dW[BTC_WGRAD_MULTI_MAX];
-  long long count[BTC_WGRAD_MULTI_MAX];
-  int S[BTC_WGRAD_MULTI_MAX];
-  int block0[BTC_WGRAD_MULTI_MAX + 1];
-  int n;
-};
-
-__global__ __launch_bounds__(256) void wgrad_reduce_multi(const ReduceJobs jobs) {
-  int j = 0;
-  while (j + 1 < jobs.n && (int)blockIdx.x >= jobs.block0[j + 1]) ++j;   // (uniform: scalar loop over <= 64 entries)
-  const long long e = (long long)((int)blockIdx.x - jobs.block0[j]) * 256 + threadIdx.x;
-  const long long count = jobs.count[j];
-  if (e >= count) return;
-  const float* __restrict__ part = jobs.part[j];
-  const int S = jobs.S[j];
-  float s = 0.f;
-  int q = 0;
-  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
-  // additions is the slab order either way)
-  for (; q + 16 <= S; q += 16) {
-    float v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) s += v[u];
-  }
-  for (; q + 8 <= S; q += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; q < S; ++q) s += part[(size_t)q * count + e];
-  jobs.dW[j][e] = s;
-}
 
 __global__ __launch_bounds__(256) void maxpool_fwd_k(const float* __restrict__ feat, const int32_t* __restrict__ nbr,
                                                      int n_out, int K, int C, float* __restrict__ out) {
@@ -1177,109 +510,6 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
   return BTC_OK;
 }
 
-template <int MT, int NT, int KB, int PH, bool BF>
-void launch_wgrad_rows_p(dim3 grid, size_t lds, hipStream_t stream, const float* g, const float* c, const int32_t* map, const int32_t* ord, int rows,
-                         int K, int Cg, int Cc, float* part, int swap) {
-  static BtcPerDeviceOnce once;   // launches come from the training thread, the autograd thread and the prefetch thread
-  btc_once_per_device(once, [] {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_rows_p<MT, NT, KB, PH, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  conv_wgrad_rows_p<MT, NT, KB, PH, BF><<<grid, 256, lds, stream>>>(g, c, map, ord, rows, K, Cg, Cc, part, swap);
-}
-
-struct WgradPlan {
-  int nt, n_cblk, n_mblk, S, tiles_per_split;
-  int rows_kernel;  // 1 = conv_wgrad_rows (row-stationary), 0 = offset-major conv_wgrad_partial
-  int mt, kb, ph, groups, swap, rows;
-  int pipe;         // rows kernel: 1 = conv_wgrad_rows_p (software-pipelined)
-  size_t lds;       // rows kernel: dynamic LDS bytes
-};
-
-size_t wgrad_rows_lds(int mt, int nt, int kb, int ph_built, int K, bool pipe) {
-  const int noff = kb * ph_built;
-  if (pipe) return (size_t)(2 * kb * TM * ldb_of(mt)) * sizeof(float) + (size_t)(3 * TM * noff + 3 * TM) * sizeof(int32_t);
-  return (size_t)(kb * TM * ldb_of(mt) + TM * ldb_of(nt)) * sizeof(float) + (size_t)(TM * K + K + TM) * sizeof(int32_t);
-}
-
-WgradPlan wgrad_plan(int n_out, int K, int Cin, int Cout, int n_in = -1, bool bf = false) {
-  WgradPlan p;
-  p.pipe = 0;
-  p.lds = 0;
-  p.rows_kernel = 0;
-  p.swap = 0;
-  p.rows = n_out;
-  {
-    // row-stationary kernel: supported (MT,NT) tile shapes and enough rows to amortise the persistent walk
-    const bool swap = n_in > 0 && 2 * n_in < n_out;  // walk the smaller side of the rulebook
-    const int rows = swap ? n_in : n_out;
-    int mt = btc_cdiv(swap ? Cout : Cin, 16), ntt = btc_cdiv(swap ? Cin : Cout, 16), kb = 0, ph = 7;
-    if (mt == 1 && ntt == 1) { kb = 8; ph = 4; }
-    else if (mt * ntt == 2) kb = 4;
-    else if (mt == 2 && ntt == 2) kb = 4;
-    else if (mt == 3 && ntt == 2) kb = 2;
-    else if (mt * ntt == 8 && (mt == 2 || mt == 4)) kb = 2;
-    else if (mt == 4 && ntt == 4) kb = 1;
-    if (kb && rows >= 4096 && K <= 64) {
-      // Work split (tools/conv_bench.py, MI355X): two workgroups per CU (512 in all) = row splits x offset groups.  More
-      // phases per group = fewer groups re-reading the dOut tile but a larger accumulator slab per workgroup (PH = 7 no
-      // longer fits two workgroups per CU) and more slab traffic; the largest PH <= 4 that still leaves >= 3 row tiles
-      // per workgroup measured best from 12 K to 210 K rows (e.g. 32->32 at 210 K rows 307 -> 219 us, at 12 K rows 63 -> 30 us).
-      const int t_ph = btc_tune_get(BTC_TUNE_WGRAD_PH), t_wgs = btc_tune_get(BTC_TUNE_WGRAD_WGS);
-      // software-pipelined variant (conv_wgrad_rows_p) when the gathered operand's channel count is a multiple of 4; it has its
-      // own (KB, PH) per tile shape (the B fragments live in registers: LDS holds the double-buffered gather tile only)
-      p.pipe = ((swap ? Cout : Cin) & (bf ? 7 : 3)) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1;   // bf16: 8-channel gathers
-      const int wgs = t_wgs ? t_wgs : 512;
-      const int n_tiles = btc_cdiv(rows, TM);
-      if (p.pipe) {
-        if (mt == 1 && ntt == 1) { kb = 4; ph = 4; }
-        else if (mt == 2 && ntt == 1) { kb = 2; ph = 8; }
-        else if (mt == 1 && ntt == 2) { kb = 4; ph = 4; }
-        else if (mt == 2 && ntt == 2) { kb = 2; ph = 8; }
-        else if (mt == 3 && ntt == 2) { kb = 2; ph = 4; }
-        else if (mt == 2 && ntt == 4) { kb = 2; ph = 4; }
-        else if (mt == 4 && ntt == 2) { kb = 1; ph = 8; }
-        else { kb = 1; ph = 4; }
-        // few tiles: half the phases per workgroup = twice the offset groups = twice the workgroups
-        if ((long long)n_tiles * btc_cdiv(K, kb * ph) < 3LL * wgs) ph >>= 1;
-        if (t_ph == ph * 2 || t_ph * 2 == ph) ph = t_ph;   // tuning runs: the other variant
-        p.lds = wgrad_rows_lds(mt, ntt, kb, ph, K, true);
-      } else {
-        if (!(mt == 1 && ntt == 1)) {
-          ph = 1;
-          for (int cand = 4; cand > 1; cand >>= 1)
-            if ((long long)n_tiles * btc_cdiv(K, kb * cand) >= 3LL * wgs) { ph = cand; break; }
-          if (t_ph) ph = t_ph;
-        }
-        const int ph_built = (mt == 1 && ntt == 1) ? 4 : ((ph == 1 || ph == 2 || ph == 4) ? ph : 7);   // the PH the launch macros instantiate
-        p.lds = wgrad_rows_lds(mt, ntt, kb, ph_built, K, false);
-      }
-      p.rows_kernel = 1;
-      p.swap = swap; p.rows = rows;
-      p.mt = mt; p.nt = ntt; p.kb = kb; p.ph = ph;
-      p.groups = btc_cdiv(K, kb * ph);
-      int S = wgs / p.groups;
-      if (S > n_tiles / 2) S = n_tiles / 2;  // at least two row tiles per persistent workgroup
-      if (S > n_tiles) S = n_tiles;
-      if (S < 1) S = 1;
-      p.S = S;
-      p.n_cblk = p.n_mblk = 1;
-      p.tiles_per_split = 0;
-      return p;
-    }
-  }
-  p.nt = Cout <= 16 ? 1 : (Cout <= 32 ? 2 : (Cout <= 64 ? 4 : 8));
-  p.n_cblk = btc_cdiv(Cout, p.nt * 16);
-  p.n_mblk = btc_cdiv(Cin, 64);
-  int n_tiles = btc_cdiv(n_out > 0 ? n_out : 1, TM);
-  int S = 1536 / (K * p.n_cblk * p.n_mblk);
-  if (S > 32) S = 32;
-  if (S < 1) S = 1;
-  if (S > n_tiles) S = n_tiles;
-  p.tiles_per_split = btc_cdiv(n_tiles, S);
-  p.S = btc_cdiv(n_tiles, p.tiles_per_split);
-  return p;
-}
-
 }  // namespace
 
 extern "C" int btc_conv_fwd(const float* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
@@ -1379,245 +609,6 @@ int btc_conv_fwd_stats(int operands, const void* src, long long src_rows, const 
   const bool bf = operands == BTC_OPERANDS_BF16_ACT;
   *fused = 1;
   return launch_apply<false>((const float*)src, W, bias, nbr, n_rows, K, Cin, Cout, (float*)dst, stream, bf, order, 0, &bn);
-}
-
-// does a weight-gradient launch take the bf16-pipe kernel?  n_feat: rows of `feat` if known (>= 0); have_bwd: the backward map was given
-// (the walk may then run over the smaller side of the rulebook)
-static bool wgrad_x_wanted(bool bf, int n_out, int n_feat, bool have_bwd, int K, int Cin, int Cout, int* mode, int* swap, int* rows) {
-  if (btc_tune_get(BTC_TUNE_WGRAD_X) == 1 || (!bf && btc_tune_get(BTC_TUNE_SPLIT) == 1) || n_feat < 0) return false;
-  *mode = bf ? 0 : 1;
-  *swap = have_bwd && n_feat > 0 && 2 * (long long)n_feat < n_out;
-  *rows = *swap ? n_feat : n_out;
-  const int cg = *swap ? Cout : Cin, cc = *swap ? Cin : Cout;
-  const long long esz = bf ? 2 : 4;
-  if (*rows < 2048 || !btc_wgrad_x_supported(*mode, K, cg, cc)) return false;
-  return (long long)n_feat * Cin * esz < 0xFFFFFF00LL && (long long)n_out * Cout * esz < 0xFFFFFF00LL;
-}
-
-extern "C" size_t btc_conv_wgrad_ws_bytes(int n_out, int K, int Cin, int Cout, int n_in) {
-  // one size for both activation types (the bf16 instances of the pipelined kernel want Cin % 8 == 0, so the two plans can differ)
-  const WgradPlan p = wgrad_plan(n_out, K, Cin, Cout, n_in, false), q = wgrad_plan(n_out, K, Cin, Cout, n_in, true);
-  int S = p.S > q.S ? p.S : q.S;
-  // ... and for the bf16-pipe kernel's split of the walk (conv_wgrad_x.hip), over either side, either activation type
-  for (int swap = 0; swap < 2; ++swap) {
-    if (swap && !(n_in > 0 && 2 * (long long)n_in < n_out)) continue;
-    const int cg = swap ? Cout : Cin, cc = swap ? Cin : Cout, rows = swap ? n_in : n_out;
-    for (int mode = 0; mode < 2 && rows >= 2048; ++mode)
-      if (btc_wgrad_x_supported(mode, K, cg, cc)) {
-        int sx = 1, ph = 1;
-        btc_wgrad_x_plan(mode, rows, K, cg, cc, &sx, &ph);
-        if (sx > S) S = sx;
-      }
-  }
-  // ... and for the narrow-result walk over the input rows (conv_wgrad_n.hip)
-  if (btc_wgrad_n_kind(K, Cin, Cout)) {
-    const int sn = btc_wgrad_n_plan(n_out), sm = n_in > 0 ? btc_wgrad_n_plan(n_in) : 0;
-    if (sn > S) S = sn;
-    if (sm > S) S = sm;
-  }
-  return btc_align((size_t)S * K * Cin * Cout * sizeof(float));
-}
-
-template <bool BF>
-static int wgrad_impl(const float* feat, const float* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
-                      int n_in, int K, int Cin, int Cout, float* dW, void* ws, size_t ws_bytes, void* stream_,
-                      const int32_t* order_out = nullptr, const int32_t* order_in = nullptr, int* slabs_out = nullptr) {
-  // slabs_out: the caller adds the slabs up itself, later (btc_wgrad_reduce_multi): *slabs_out = S > 0 slabs of K Cin Cout floats
-  // in `ws`, dW untouched -- or 0: dW is complete (no rows: zeros)
-  hipStream_t stream = (hipStream_t)stream_;
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_wgrad: bad sizes");
-  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_wgrad: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
-  // rows of `feat`: n_in when the backward map comes with it, or when a caller without one states a positive count; a legacy call that
-  // passes NULL and 0 (the argument used to be ignored without a map) leaves it unknown -> the fp32-pipe kernels, which need no bound
-  // nbr_in == nbr_out (the same pointer, n_in == n_out): a submanifold layer -- its backward map is the forward map with the offset index
-  // mirrored, nothing else is stored (rulebook.hip); the kernels that walk the output rows take it as "no backward map"
-  const bool mirror = nbr_in != nullptr && nbr_in == nbr_out && n_in == n_out;
-  if (mirror) nbr_in = nullptr;
-  const int n_feat = (nbr_in || n_in > 0) ? n_in : -1;
-  if (!nbr_in) n_in = -1;
-  BTC_CHECK_ARG(ws_bytes >= btc_conv_wgrad_ws_bytes(n_out, K, Cin, Cout, n_in), "btc_conv_wgrad: workspace too small");
-  long long count = (long long)K * Cin * Cout;
-  if (slabs_out) *slabs_out = 0;
-  if (n_out <= 0) {
-    BTC_HIP(hipMemsetAsync(dW, 0, (size_t)count * sizeof(float), stream));
-    return BTC_OK;
-  }
-  WgradPlan p = wgrad_plan(n_out, K, Cin, Cout, n_in, BF);
-  float* part = (float*)ws;
-  // every path below ends with the same reduction of p.S slabs
-#define BTC_WGRAD_FINISH()                                                             \
-  do {                                                                                 \
-    BTC_LAUNCH_CHECK();                                                                \
-    if (slabs_out) {                                                                   \
-      *slabs_out = p.S;                                                                \
-    } else {                                                                           \
-      wgrad_reduce<<<btc_cdiv(count, 256), 256, 0, stream>>>(part, p.S, count, dW);    \
-      BTC_LAUNCH_CHECK();                                                              \
-    }                                                                                  \
-    return BTC_OK;                                                                     \
-  } while (0)
-  const int n_kind = btc_tune_get(BTC_TUNE_WGRAD_NARROW) != 1 ? btc_wgrad_n_kind(K, Cin, Cout) : 0;
-  if (n_kind == 1 && (mirror || nbr_in)) {
-    // narrow result side (the 5-channel occupancy head): walk the layer's INPUT rows -- x read once, dy gathered (conv_wgrad_n.hip).
-    // 32-bit byte offsets: map and both operands under 4 GB.
-    const long long rows = mirror ? n_out : n_in, esz = BF ? 2 : 4;
-    if (rows >= 2048 && rows * K * 4 < 0xFFFFFF00LL && rows * Cin * esz < 0xFFFFFF00LL && (long long)n_out * Cout * esz < 0xFFFFFF00LL) {
-      p.S = btc_wgrad_n_plan((int)rows);
-      const int rc = btc_launch_wgrad_n(BF, feat, dout, mirror ? nbr_out : nbr_in, (int)rows, K, Cin, Cout, part, mirror ? 1 : 0, stream);
-      if (rc != BTC_OK) return rc;
-      BTC_WGRAD_FINISH();
-    }
-  }
-  if (n_kind == 2 && n_feat >= 0 && !(nbr_in && 2 * (long long)n_feat < n_out)) {
-    // narrow input side (the 4- / 6-channel first layers): walk the OUTPUT rows -- dOut read once, the features gathered through nbr_out
-    // (not where the rulebook's input side is less than half the output side: the kernels below walk that side -- 4 -> 16 from 8.4 K to
-    // 40 K rows: 13.6 us there, 23.8 here)
-    const long long esz = BF ? 2 : 4;
-    if (n_out >= 2048 && (long long)n_out * K * 4 < 0xFFFFFF00LL && (long long)n_out * Cout * esz < 0xFFFFFF00LL && (long long)n_feat * Cin * esz < 0xFFFFFF00LL) {
-      p.S = btc_wgrad_n_plan(n_out);
-      const int rc = btc_launch_wgrad_n(BF, dout, feat, nbr_out, n_out, K, Cout, Cin, part, 2, stream);
-      if (rc != BTC_OK) return rc;
-      BTC_WGRAD_FINISH();
-    }
-  }
-  {
-    // the row-stationary walk on the bf16 matrix pipe (conv_wgrad_x.hip): bf16 activations as they are, fp32 activations as three exact
-    // bf16 pieces; any channel counts whose gathered side is a multiple of 16 (a workgroup owns a <= 64 x 64 block of every dW[k]).
-    // Its gathers use 32-bit byte offsets: both operands must stay under 4 GB, and the row count of `feat` must be known.
-    int x_mode, x_swap, x_rows;
-    if (wgrad_x_wanted(BF, n_out, n_feat, nbr_in != nullptr, K, Cin, Cout, &x_mode, &x_swap, &x_rows)) {
-      const int cg = x_swap ? Cout : Cin, cc = x_swap ? Cin : Cout;
-      int ph = 1;
-      btc_wgrad_x_plan(x_mode, x_rows, K, cg, cc, &p.S, &ph);
-      const int rc = btc_launch_wgrad_x(x_mode, x_swap ? (const void*)dout : (const void*)feat, x_swap ? (const void*)feat : (const void*)dout,
-                                        x_swap ? nbr_in : nbr_out, x_swap ? order_in : order_out, x_rows, K, cg, cc, part, x_swap, stream);
-      if (rc != BTC_OK) return rc;
-      BTC_WGRAD_FINISH();
-    }
-  }
-  if (p.rows_kernel) {
-    // operands of the walk: gathered rows (via the map) and contiguous rows, see conv_wgrad_rows
-    const float* g_ = p.swap ? dout : feat;
-    const float* c_ = p.swap ? feat : dout;
-    const int32_t* map_ = p.swap ? nbr_in : nbr_out;
-    const int32_t* ord_ = p.swap ? order_in : order_out;
-    const int Cg = p.swap ? Cout : Cin, Cc = p.swap ? Cin : Cout;
-    dim3 grid(p.S, p.groups);
-    const size_t lds = p.lds;
-    if (p.pipe) {
-#define BTC_WGP2(MT_, NT_, KB_, PH_) launch_wgrad_rows_p<MT_, NT_, KB_, PH_, BF>(grid, lds, stream, g_, c_, map_, ord_, p.rows, K, Cg, Cc, part, p.swap)
-#define BTC_WGP(MT_, NT_, KB_, PH_)                  \
-  do {                                               \
-    if (p.ph == PH_) BTC_WGP2(MT_, NT_, KB_, PH_);   \
-    else BTC_WGP2(MT_, NT_, KB_, (PH_ / 2));         \
-  } while (0)
-      if (p.mt == 1 && p.nt == 1) BTC_WGP(1, 1, 4, 4);
-      else if (p.mt == 2 && p.nt == 1) BTC_WGP(2, 1, 2, 8);
-      else if (p.mt == 1 && p.nt == 2) BTC_WGP(1, 2, 4, 4);
-      else if (p.mt == 2 && p.nt == 2) BTC_WGP(2, 2, 2, 8);
-      else if (p.mt == 3 && p.nt == 2) BTC_WGP(3, 2, 2, 4);
-      else if (p.mt == 2 && p.nt == 4) BTC_WGP(2, 4, 2, 4);
-      else if (p.mt == 4 && p.nt == 2) BTC_WGP(4, 2, 1, 8);
-      else BTC_WGP(4, 4, 1, 4);
-#undef BTC_WGP
-#undef BTC_WGP2
-      BTC_WGRAD_FINISH();
-    }
-#define BTC_WG_ROWS(MT_, NT_, KB_, PH_) \
-  conv_wgrad_rows<MT_, NT_, KB_, PH_, BF><<<grid, 256, lds, stream>>>(g_, c_, map_, ord_, p.rows, K, Cg, Cc, part, p.swap, btc_tune_get(BTC_TUNE_APPLY_DEBUG))
-#define BTC_WG_ROWS_PH(MT_, NT_, KB_)               \
-  do {                                              \
-    if (p.ph == 1) BTC_WG_ROWS(MT_, NT_, KB_, 1);   \
-    else if (p.ph == 2) BTC_WG_ROWS(MT_, NT_, KB_, 2); \
-    else if (p.ph == 4) BTC_WG_ROWS(MT_, NT_, KB_, 4); \
-    else BTC_WG_ROWS(MT_, NT_, KB_, 7);             \
-  } while (0)
-    if (p.mt == 1 && p.nt == 1) BTC_WG_ROWS(1, 1, 8, 4);
-    else if (p.mt == 2 && p.nt == 1) BTC_WG_ROWS_PH(2, 1, 4);
-    else if (p.mt == 1 && p.nt == 2) BTC_WG_ROWS_PH(1, 2, 4);
-    else if (p.mt == 2 && p.nt == 2) BTC_WG_ROWS_PH(2, 2, 4);
-    else if (p.mt == 3 && p.nt == 2) BTC_WG_ROWS_PH(3, 2, 2);
-    else if (p.mt == 2 && p.nt == 4) BTC_WG_ROWS_PH(2, 4, 2);
-    else if (p.mt == 4 && p.nt == 2) BTC_WG_ROWS_PH(4, 2, 2);
-    else BTC_WG_ROWS_PH(4, 4, 1);
-#undef BTC_WG_ROWS_PH
-#undef BTC_WG_ROWS
-    BTC_WGRAD_FINISH();
-  }
-  dim3 grid(K, p.S, p.n_mblk * p.n_cblk);
-  size_t lds = (size_t)(TM * WG_LDA + TM * ldb_of(p.nt)) * sizeof(float) + (4 * TM + 2) * sizeof(int32_t);
-  if (((Cin | Cout) & 3) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1) {
-    switch (p.nt) {
-      case 1: conv_wgrad_partial_p<1, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-      case 2: conv_wgrad_partial_p<2, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-      case 4: conv_wgrad_partial_p<4, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-      default: conv_wgrad_partial_p<8, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-    }
-    BTC_WGRAD_FINISH();
-  }
-  switch (p.nt) {
-    case 1: conv_wgrad_partial<1, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-    case 2: conv_wgrad_partial<2, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-    case 4: conv_wgrad_partial<4, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-    default: conv_wgrad_partial<8, BF><<<grid, 256, lds, stream>>>(feat, dout, nbr_out, n_out, K, Cin, Cout, p.tiles_per_split, p.n_cblk, part); break;
-  }
-  BTC_WGRAD_FINISH();
-#undef BTC_WGRAD_FINISH
-}
-
-extern "C" int btc_conv_wgrad(const float* feat, const float* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
-                              int n_in, int K, int Cin, int Cout, float* dW, void* ws, size_t ws_bytes, void* stream) {
-  return wgrad_impl<false>(feat, dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream);
-}
-
-extern "C" int btc_conv_wgrad_bf16(const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
-                                   int n_in, int K, int Cin, int Cout, float* dW, void* ws, size_t ws_bytes, void* stream) {
-  return wgrad_impl<true>((const float*)feat, (const float*)dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream);
-}
-
-extern "C" int btc_conv_wgrad_ordered(int bf16_act, const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
-                                      int n_in, const int32_t* order_out, const int32_t* order_in, int K, int Cin, int Cout, float* dW, void* ws,
-                                      size_t ws_bytes, void* stream) {
-  if (bf16_act)
-    return wgrad_impl<true>((const float*)feat, (const float*)dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out,
-                            order_in);
-  return wgrad_impl<false>((const float*)feat, (const float*)dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out,
-                           order_in);
-}
-
-extern "C" int btc_conv_wgrad_slabs(int bf16_act, const void* feat, const void* dout, const int32_t* nbr_out, int n_out, const int32_t* nbr_in,
-                                    int n_in, const int32_t* order_out, const int32_t* order_in, int K, int Cin, int Cout, float* dW, void* ws,
-                                    size_t ws_bytes, int* n_slabs, void* stream) {
-  BTC_CHECK_ARG(n_slabs != nullptr, "btc_conv_wgrad_slabs: n_slabs is NULL");
-  if (bf16_act)
-    return wgrad_impl<true>((const float*)feat, (const float*)dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out,
-                            order_in, n_slabs);
-  return wgrad_impl<false>((const float*)feat, (const float*)dout, nbr_out, n_out, nbr_in, n_in, K, Cin, Cout, dW, ws, ws_bytes, stream, order_out,
-                           order_in, n_slabs);
-}
-
-extern "C" int btc_wgrad_reduce_multi(const float* const* parts, float* const* dWs, const int* n_slabs, const long long* counts, int n_jobs,
-                                      void* stream) {
-  BTC_CHECK_ARG(n_jobs >= 0 && (n_jobs == 0 || (parts && dWs && n_slabs && counts)), "btc_wgrad_reduce_multi: bad arguments");
-  for (int base = 0; base < n_jobs; base += BTC_WGRAD_MULTI_MAX) {
-    ReduceJobs jobs;
-    jobs.n = n_jobs - base < BTC_WGRAD_MULTI_MAX ? n_jobs - base : BTC_WGRAD_MULTI_MAX;
-    long long blocks = 0;
-    for (int j = 0; j < jobs.n; ++j) {
-      BTC_CHECK_ARG(n_slabs[base + j] >= 1 && counts[base + j] >= 1 && parts[base + j] && dWs[base + j], "btc_wgrad_reduce_multi: bad job %d", base + j);
-      jobs.part[j] = parts[base + j];
-      jobs.dW[j] = dWs[base + j];
-      jobs.S[j] = n_slabs[base + j];
-      jobs.count[j] = counts[base + j];
-      jobs.block0[j] = (int)blocks;
-      blocks += (counts[base + j] + 255) / 256;
-    }
-    jobs.block0[jobs.n] = (int)blocks;
-    BTC_CHECK_ARG(blocks < (1LL << 31), "btc_wgrad_reduce_multi: too many elements");
-    wgrad_reduce_multi<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(jobs);
-    BTC_LAUNCH_CHECK();
-  }
-  return BTC_OK;
 }
 
 extern "C" int btc_maxpool_fwd(const float* feat, const int32_t* nbr_out, int n_out, int K, int C, float* out, void* stream) {

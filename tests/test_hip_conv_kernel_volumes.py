@@ -1,6 +1,6 @@
 """Sparse-conv kernels at kernel volumes other than 3 x 3 x 3, at tile edges and at the row counts where the dispatch policy switches.
 
-Every family of csrc/sparse_conv.hip, conv_apply_glds.hip, conv_apply_split.hip, conv_apply_bf16.hip, conv_wgrad_x.hip and conv_wgrad_n.hip
+Every family of csrc/sparse_conv.hip, conv_apply_glds.hip, conv_apply_split.hip, conv_apply_bf16.hip, conv_wgrad.hip, conv_wgrad_x.hip and conv_wgrad_n.hip
 takes the number of offsets K at run time: the per-wave offset ballot (64 bits), the compact offset lists, PAIR's odd tail, z-split's item
 count, the K-sized map tiles in LDS and the offset groups of the weight-gradient walks all depend on it.  Here each family runs at K from 1
 to 512 on synthetic maps (tests/conv_ref.py: exact row counts, rows without neighbours, rows with all K offsets, an offset missing from

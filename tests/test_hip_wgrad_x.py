@@ -87,7 +87,7 @@ def _x_shape(mode, cg, cc):
 
 
 def _x_applies(mode, rb, n_src, cin, cout):
-    """does the launch take conv_wgrad_x?  (the policy of sparse_conv.hip wgrad_x_wanted: the row-stationary walk, over the smaller side)"""
+    """does the launch take conv_wgrad_x?  (the policy of conv_wgrad.hip wgrad_choose: the row-stationary walk, over the smaller side)"""
     n_out = rb.nbr_out.shape[0]
     swap = (not rb.mirrored) and 2 * n_src < n_out
     rows, cg, cc = (n_src, cout, cin) if swap else (n_out, cin, cout)

@@ -1,5 +1,5 @@
 """Weight-gradient launches of one bench step, one by one (HIP events, one stream): us, algorithmic GB/s and TFLOP/s, and the
-same launch on the fp32-pipe kernels (BTC_TUNE_WGRAD_X = 1: conv_wgrad_rows_p / conv_wgrad_partial_p)."""
+same launch on the fp32-pipe kernels (BTC_TUNE_WGRAD_X = 1: conv_wgrad_rows_p / conv_wgrad_partial_p of csrc/conv_wgrad.hip)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
