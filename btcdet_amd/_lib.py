@@ -1,4 +1,4 @@
-"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h).
+"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h and include/btcdet_hip_infer.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -181,6 +181,13 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
+# the entry points of the second public header, include/btcdet_hip_infer.h (same library, same rules)
+_INFER_SIGS = {
+    "btc_conv_bn_eval_fwd": (ci, [ci, vp, ctypes.c_longlong, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]),
+}
+
+INFER_EXPORTED_SYMBOLS = tuple(_INFER_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -191,7 +198,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/btcdet_hip.h"
+#include "../../include/btcdet_hip_infer.h"
 
 namespace {
 
@@ -262,6 +263,51 @@ std::tuple<Tensor, Tensor, Tensor> conv_bn_fwd(const Tensor& features, const Ten
   Tensor x = conv_fwd(features, w, bias, map_fwd, order_fwd, stream);
   auto ys = bn_fwd(x, gamma, beta, rm, rv, nbt, use_batch, momentum, eps, relu, ws, ws_bytes, stream);
   return std::make_tuple(x, std::get<0>(ys), std::get<1>(ys));
+}
+
+// conv -> BatchNorm (eval: running statistics) -> ReLU of a forward pass nobody differentiates: ONE launch, the transform in the conv
+// kernel's epilogue (btc_conv_bn_eval_fwd, include/btcdet_hip_infer.h) -- no x, no statistics, no BatchNorm workspace.  Weights are
+// prepared as conv_bn_fwd prepares them (same policy functions), so the two routes pick the same kernel and give the same bits.
+std::atomic<int64_t> g_eval_fold_calls{0};
+
+Tensor conv_bn_eval_fold(const Tensor& features, const Tensor& w, const OptTensor& bias, const Tensor& map_fwd, const OptTensor& order_fwd,
+                         const OptTensor& gamma, const OptTensor& beta, const Tensor& rm, const Tensor& rv, double eps, bool relu, int64_t stream) {
+  const int64_t cin = w.size(-2), cout = w.size(-1), K = map_fwd.size(1), n_res = map_fwd.size(0);
+  need(features.is_contiguous() && w.is_contiguous() && map_fwd.is_contiguous(), "conv_bn_eval_fold: contiguous tensors expected");
+  need(w.numel() == K * cin * cout && features.size(1) == cin, "conv_bn_eval_fold: weight does not match the rulebook / features");
+  need(rm.defined() && rv.defined() && rm.numel() == cout && rv.numel() == cout, "conv_bn_eval_fold: running statistics of the result channels expected");
+  const int32_t* order = order_ptr(order_fwd, n_res, "conv_bn_eval_fold: the row order does not match the map");
+  Tensor y = at::empty({n_res, cout}, features.options());
+  int operands = features.scalar_type() == at::kBFloat16 ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32;
+  const void* wp = w.data_ptr();
+  Tensor q;
+  if (bf16_operands(features, K, cin, cout)) {
+    q = weights_bf16(w, K, cin, cout, stream);
+    operands = BTC_OPERANDS_BF16;
+    wp = (const char*)q.data_ptr() + 2 * w.numel();
+  } else if (split_operands(features, K, cin, cout, n_res, stream)) {
+    q = weights_q(w, K, cin, cout, stream, 3);
+    operands = BTC_OPERANDS_F32_SPLIT;
+    wp = (const char*)q.data_ptr() + 6 * w.numel();
+  }
+  chk(btc_conv_bn_eval_fwd(operands, features.data_ptr(), (long long)features.size(0), wp, fptr(bias), (const int32_t*)map_fwd.data_ptr(), order,
+                           (int)n_res, (int)K, (int)cin, (int)cout, fptr(gamma), fptr(beta), (const float*)rm.data_ptr(), (const float*)rv.data_ptr(),
+                           (float)eps, (int)relu, y.data_ptr(), st(stream)), "btc_conv_bn_eval_fwd");
+  ++g_eval_fold_calls;
+  return y;
+}
+
+int64_t eval_fold_calls() { return g_eval_fold_calls.load(); }
+
+// the fold is taken when the BatchNorm reads its running statistics AND nothing will ask for a gradient through the node (eval mode
+// WITH gradients -- frozen-statistics fine-tuning -- keeps the autograd node: its backward reads x); BTC_TUNE_EVAL_FOLD = 1: never
+bool eval_fold_wanted(const Tensor& features, const Tensor& weight, const OptTensor& bias, const Tensor& map_fwd, const OptTensor& gamma,
+                      const OptTensor& beta, const OptTensor& rm, const OptTensor& rv, bool use_batch) {
+  if (use_batch || map_fwd.size(0) < 1 || !(rm.has_value() && rm->defined() && rv.has_value() && rv->defined())) return false;
+  if (btc_tune_value(BTC_TUNE_EVAL_FOLD) == 1) return false;
+  if (!at::GradMode::is_enabled()) return true;
+  auto rg = [](const OptTensor& t) { return t.has_value() && t->defined() && t->requires_grad(); };
+  return !(features.requires_grad() || weight.requires_grad() || rg(bias) || rg(gamma) || rg(beta));
 }
 
 // dx, dparam (2, C) = dgamma | dbeta
@@ -731,6 +777,8 @@ struct ConvBNReLUNode : public torch::autograd::Function<ConvBNReLUNode> {
 Tensor conv_bn_relu(const Tensor& features, const Tensor& weight, const OptTensor& bias, const Tensor& map_fwd, const Tensor& map_bwd,
                     const OptTensor& order_fwd, const OptTensor& order_bwd, const OptTensor& gamma, const OptTensor& beta, const OptTensor& rm, const OptTensor& rv, const OptTensor& nbt, bool use_batch,
                     double momentum, double eps, bool relu, const Tensor& ws, int64_t ws_bytes, bool overlap, bool allow_defer) {
+  if (eval_fold_wanted(features, weight, bias, map_fwd, gamma, beta, rm, rv, use_batch))
+    return conv_bn_eval_fold(features, weight, bias, map_fwd, order_fwd, gamma, beta, *rm, *rv, eps, relu, current_stream());
   return ConvBNReLUNode::apply(features, weight, bias, map_fwd, map_bwd, order_fwd, order_bwd, gamma, beta, rm, rv, nbt, use_batch, momentum, eps, relu, ws, ws_bytes,
                                overlap, allow_defer);
 }
@@ -1012,9 +1060,14 @@ Tensor conv_bn_relu_chain(const Tensor& features, const std::vector<Tensor>& wei
            ws_bytes.size() == L && overlaps.size() == L && allow_defers.size() == L,
        "conv_bn_relu_chain: per-layer argument lists differ in length");
   Tensor x = features;
-  for (size_t i = 0; i < L; ++i)
+  for (size_t i = 0; i < L; ++i) {
+    if (eval_fold_wanted(x, weights[i], biases[i], map_fwd[i], gammas[i], betas[i], rms[i], rvs[i], use_batch[i])) {
+      x = conv_bn_eval_fold(x, weights[i], biases[i], map_fwd[i], order_fwd[i], gammas[i], betas[i], *rms[i], *rvs[i], epss[i], relus[i], current_stream());
+      continue;
+    }
     x = ConvBNReLUNode::apply(x, weights[i], biases[i], map_fwd[i], map_bwd[i], order_fwd[i], order_bwd[i], gammas[i], betas[i], rms[i], rvs[i], nbts[i], use_batch[i],
                               momenta[i], epss[i], relus[i], ws, ws_bytes[i], overlaps[i], allow_defers[i]);
+  }
   return x;
 }
 
@@ -1109,6 +1162,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd", &conv_fwd, py::call_guard<py::gil_scoped_release>());
   m.def("bn_fwd", &bn_fwd, py::call_guard<py::gil_scoped_release>());
   m.def("conv_bn_fwd", &conv_bn_fwd, py::call_guard<py::gil_scoped_release>());
+  m.def("conv_bn_eval_fold", &conv_bn_eval_fold, py::call_guard<py::gil_scoped_release>());
+  m.def("eval_fold_calls", &eval_fold_calls);
   m.def("bn_bwd", &bn_bwd, py::call_guard<py::gil_scoped_release>());
   m.def("conv_bwd", &conv_bwd, py::call_guard<py::gil_scoped_release>());
   m.def("conv_bn_relu", &conv_bn_relu, py::call_guard<py::gil_scoped_release>());

@@ -11,6 +11,7 @@
 //   bn_apply / bn_bwd_apply : elementwise, float4
 #include "btc_common.h"
 #include "bn_fuse.h"
+#include "../../include/btcdet_hip_infer.h"
 
 namespace {
 
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(BN_T) void bn_eval_stats(const float* __restrict__ 
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   mean_out[c] = running_mean[c];
-  rstd_out[c] = 1.0f / sqrtf(running_var[c] + eps);
+  rstd_out[c] = bn_rstd_eval(running_var[c], eps);
 }
 
 template <bool VEC, bool BF>
@@ -197,15 +198,13 @@ __global__ __launch_bounds__(BN_T) void bn_apply(const float* __restrict__ x, co
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float g = gamma ? gamma[c + j] : 1.f, b = beta ? beta[c + j] : 0.f;
-      float t = (o[j] - mean[c + j]) * rstd[c + j] * g + b;
-      o[j] = relu ? fmaxf(t, 0.f) : t;
+      o[j] = bn_affine(o[j], mean[c + j], rstd[c + j], g, b, relu);
     }
     btc_st4<BF>(y, i, o[0], o[1], o[2], o[3]);
   } else {
     int c = (int)(i % C);
     float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    float t = (btc_ld1<BF>(x, i) - mean[c]) * rstd[c] * g + b;
-    btc_st1<BF>(y, i, relu ? fmaxf(t, 0.f) : t);
+    btc_st1<BF>(y, i, bn_affine(btc_ld1<BF>(x, i), mean[c], rstd[c], g, b, relu));
   }
 }
 
@@ -588,7 +587,7 @@ extern "C" int btc_conv_bn_relu_fwd_src(int operands, const void* src, long long
   const bool bf = operands == BTC_OPERANDS_BF16_ACT || operands == BTC_OPERANDS_BF16;
   int fused = 0;
   if (fuse_ws && Cout <= BN_FUSE_CMAX && btc_tune_get(BTC_TUNE_BN_FUSE) != 1) {
-    BnFuse bn;
+    BnFuse bn = btc_bn_fuse_none();   // (statistics mode: the eval-mode fields stay null)
     bn.counter = (int32_t*)fuse_ws;
     bn.slots = (double*)((char*)fuse_ws + 256);
     bn.mean_out = save_mean; bn.rstd_out = save_rstd;
@@ -605,4 +604,20 @@ extern "C" int btc_conv_bn_relu_fwd_src(int operands, const void* src, long long
                              (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused != 0);
   return bn_fwd_impl<false>((const float*)x, n_rows, Cout, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, 1, relu,
                             (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused != 0);
+}
+
+// ---- conv -> BatchNorm (eval: running statistics) -> ReLU in ONE launch: the affine and the ReLU in the conv's epilogue, only y is written
+// (bn_fuse.h, second mode; a z-split launch of the split-operand kernel applies them in its reduction)
+extern "C" int btc_conv_bn_eval_fwd(int operands, const void* src, long long src_rows, const void* W, const float* bias, const int32_t* nbr,
+                                    const int32_t* order, int n_rows, int K, int Cin, int Cout, const float* gamma, const float* beta,
+                                    const float* running_mean, const float* running_var, float eps, int relu, void* y, void* stream) {
+  BTC_CHECK_ARG(n_rows >= 1, "btc_conv_bn_eval_fwd: empty input");
+  BTC_CHECK_ARG(operands >= BTC_OPERANDS_F32 && operands <= BTC_OPERANDS_F32_SPLIT, "btc_conv_bn_eval_fwd: operands=%d", operands);
+  BTC_CHECK_ARG(running_mean && running_var, "btc_conv_bn_eval_fwd: eval mode needs running statistics");
+  BTC_CHECK_ARG(src && W && nbr && y, "btc_conv_bn_eval_fwd: null operand");
+  BnFuse bn = btc_bn_fuse_none();
+  bn.ev_mean = running_mean; bn.ev_var = running_var; bn.ev_gamma = gamma; bn.ev_beta = beta; bn.ev_relu = relu ? 1 : 0;
+  bn.eps = eps; bn.N = n_rows; bn.C = Cout;
+  int fused = 0;
+  return btc_conv_fwd_stats(operands, src, src_rows, (const float*)W, bias, nbr, order, n_rows, K, Cin, Cout, y, bn, (hipStream_t)stream, &fused);
 }

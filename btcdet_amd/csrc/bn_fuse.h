@@ -30,6 +30,14 @@ struct BnFuse {
   float momentum, eps;
   int N, C;
   int nslots;           // power of two, 32 .. BN_FUSE_SLOTS_MAX
+  // second mode (ev_mean != nullptr; slots == nullptr): the layer's BatchNorm is in eval mode and nobody needs the conv result itself --
+  // the forward epilogues apply the running-statistics affine (+ ReLU) to the tile in registers and store y where they would have
+  // stored x (bn_eval_col / bn_affine below; eps and C as above).  All four arrays are read-only.
+  const float* ev_mean;   // [C] running mean
+  const float* ev_var;    // [C] running variance
+  const float* ev_gamma;  // [C] or nullptr
+  const float* ev_beta;   // [C] or nullptr
+  int ev_relu;
 };
 
 static inline size_t btc_bn_fuse_bytes() { return 256 + (size_t)BN_FUSE_SLOTS_MAX * 2 * BN_FUSE_CMAX * sizeof(double); }
@@ -44,7 +52,30 @@ static inline BnFuse btc_bn_fuse_none() {
   BnFuse b;
   b.slots = nullptr; b.counter = nullptr; b.mean_out = b.rstd_out = b.running_mean = b.running_var = nullptr; b.num_batches = nullptr;
   b.momentum = b.eps = 0.f; b.N = b.C = 0; b.nslots = 32;
+  b.ev_mean = b.ev_var = b.ev_gamma = b.ev_beta = nullptr; b.ev_relu = 0;
   return b;
+}
+
+// ---- the BatchNorm transform of ONE element, stated once: bn_apply (bn.hip) and every conv epilogue's eval mode go through these, so the
+// folded launch and conv -> bn_eval_stats -> bn_apply give the same bits.  Every operation is pinned to its own rounding (no fma
+// contraction, whatever the translation unit's flags say).
+__device__ __forceinline__ float bn_rstd_eval(float running_var, float eps) { return 1.0f / sqrtf(__fadd_rn(running_var, eps)); }
+
+__device__ __forceinline__ float bn_affine(float v, float mean, float rstd, float g, float b, int relu) {
+  const float t = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(v, mean), rstd), g), b);
+  return relu ? fmaxf(t, 0.f) : t;
+}
+
+// the per-channel constants of a column in eval mode (C <= 1024 floats per array: straight from L2, no LDS -- the apply kernels have none left)
+struct BnEvalCol { float m, rs, g, b; };
+__device__ __forceinline__ BnEvalCol bn_eval_col(const BnFuse& bn, int col) {
+  BnEvalCol k;
+  const bool in = col < bn.C;
+  k.m = in ? bn.ev_mean[col] : 0.f;
+  k.rs = in ? bn_rstd_eval(bn.ev_var[col], bn.eps) : 0.f;
+  k.g = (in && bn.ev_gamma) ? bn.ev_gamma[col] : 1.f;
+  k.b = (in && bn.ev_beta) ? bn.ev_beta[col] : 0.f;
+  return k;
 }
 
 // one wave's NT 16 x 16 tiles in the MFMA C/D layout (column = lane & 15, rows (lane >> 4) * 4 + r): v[nt][r] the values as STORED

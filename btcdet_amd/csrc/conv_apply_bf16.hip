@@ -197,14 +197,18 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
   // C/D layout of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
   float vals[NTW][4];
   bool valid[4];
+  const bool ev = bn.ev_mean != nullptr;   // (bn_fuse.h, second mode)
 #pragma unroll
   for (int nt = 0; nt < NTW; ++nt) {
     const int col = n0 + (wc * NTW + nt) * 16 + (lane & 15);
     const float bv0 = bias ? bias[col] : 0.f;
+    BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
+    if (ev) ec = bn_eval_col(bn, col);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = s_row[wr * 16 + kq * 4 + r];
-      const unsigned short h = btc_f32_to_bf16(bias ? (acc[nt][r] + bv0) : acc[nt][r]);
+      unsigned short h = btc_f32_to_bf16(bias ? (acc[nt][r] + bv0) : acc[nt][r]);
+      if (ev) h = btc_f32_to_bf16(bn_affine(btc_bf16_to_f32(h), ec.m, ec.rs, ec.g, ec.b, bn.ev_relu));   // eval-mode BatchNorm (+ ReLU) of x as stored: y
       if (row >= 0) out[(size_t)row * Cres + col] = h;
       valid[r] = row >= 0;
       vals[nt][r] = btc_bf16_to_f32(h);   // the value as STORED: what the BatchNorm behind this layer reads

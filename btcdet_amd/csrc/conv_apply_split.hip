@@ -335,16 +335,20 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
     }
 
     // epilogue as conv_apply_g's: C/D layout of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
+    const bool ev = bn.ev_mean != nullptr;   // (bn_fuse.h, second mode; a z-split launch gets none: split_reduce applies it)
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
       const int col = n0 + (wc * NTW + nt) * 16 + (lane & 15);
       const float bv0 = bias ? bias[col] : 0.f;
+      BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
+      if (ev) ec = bn_eval_col(bn, col);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = s_row[wr * 16 + kg * 4 + r];
         valid[r] = row >= 0;
         const float sum = acc[nt][r] + (accm[nt][r] + accs[nt][r]);
-        const float v = bias ? (sum + bv0) : sum;
+        float v = bias ? (sum + bv0) : sum;
+        if (ev) v = bn_affine(v, ec.m, ec.rs, ec.g, ec.b, bn.ev_relu);   // eval-mode BatchNorm (+ ReLU) folded in: y, not x
         if (row >= 0) out[(size_t)row * Cres + col] = v;
         vals[nt][r] = v;
       }
@@ -390,6 +394,12 @@ __global__ __launch_bounds__(256) void split_reduce(const float* __restrict__ sl
   const size_t slab = (size_t)n_rows * Cres;
   const f32x4 b = bias ? *(const f32x4*)(bias + col) : (f32x4){0.f, 0.f, 0.f, 0.f};
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+  const bool ev = bn.ev_mean != nullptr;   // eval-mode BatchNorm (+ ReLU) of the summed rows (bn_fuse.h, second mode)
+  BnEvalCol ec[4] = {};
+  if (ev) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ec[e] = bn_eval_col(bn, col + e);
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int row = row0 + i * 4 + rq;
@@ -398,6 +408,10 @@ __global__ __launch_bounds__(256) void split_reduce(const float* __restrict__ sl
       f32x4 v = *(const f32x4*)p;
       for (int z = 1; z < Z; ++z) v += *(const f32x4*)(p + z * slab);
       if (bias) v += b;
+      if (ev) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = bn_affine(v[e], ec[e].m, ec[e].rs, ec[e].g, ec[e].b, bn.ev_relu);
+      }
       *(f32x4*)(out + (size_t)row * Cres + col) = v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {

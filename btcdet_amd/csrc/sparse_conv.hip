@@ -190,16 +190,20 @@ __global__ __launch_bounds__(THREADS) void conv_apply(const float* __restrict__ 
   // ---- epilogue: C/D layout of 16x16: col = lane&15, row = (lane>>4)*4 + reg
   float vals[NT][4];
   bool valid[4];
+  const bool ev = !TRANS_W && bn.ev_mean != nullptr;   // (bn_fuse.h, second mode; forward instances only)
 #pragma unroll
   for (int r = 0; r < 4; ++r) valid[r] = row0 + wave * 16 + kq * 4 + r < n_rows;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int col = n0 + nt * 16 + (lane & 15);
     const float bv0 = (bias && col < Cres) ? bias[col] : 0.f;
+    BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
+    if (ev) ec = bn_eval_col(bn, col);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = row0 + wave * 16 + kq * 4 + r;
       vals[nt][r] = bias ? (acc[nt][r] + bv0) : acc[nt][r];
+      if (ev) vals[nt][r] = bn_affine(vals[nt][r], ec.m, ec.rs, ec.g, ec.b, bn.ev_relu);   // eval-mode BatchNorm (+ ReLU) folded in: y, not x
       if (col < Cres && row < n_rows) out[(size_t)row * Cres + col] = vals[nt][r];
     }
   }
@@ -228,7 +232,9 @@ __host__ __device__ inline size_t ws_lds_bytes(int K, int Cred, int nt) {
   return (size_t)K * crp * (nt * 16) * sizeof(float) + (size_t)WS_WAVES * 16 * K * sizeof(int32_t);
 }
 
-template <int NT, bool TRANS_W>
+// EV: the eval-mode BatchNorm epilogue (bn_fuse.h, second mode) is a TEMPLATE parameter of this family: as a run-time branch it cost the
+// two-tile forward instance 7 registers and its fifth wave per SIMD
+template <int NT, bool TRANS_W, bool EV = false>
 __global__ __launch_bounds__(WS_WAVES * 64) void conv_apply_ws(const float* __restrict__ feat, const float* __restrict__ W,
                                                               const float* __restrict__ bias, const int32_t* __restrict__ nbr,
                                                               int n_rows, int K, int Cred, int Cres, float* __restrict__ out, int mirror,
@@ -328,16 +334,20 @@ __global__ __launch_bounds__(WS_WAVES * 64) void conv_apply_ws(const float* __re
 #undef WS_MATH
     float vals[NT][4];
     bool valid[4];
+    constexpr bool ev = EV;
 #pragma unroll
     for (int r = 0; r < 4; ++r) valid[r] = row0 + kq * 4 + r < n_rows;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int col = nt * 16 + lrow;
       const float bv0 = (bias && col < Cres) ? bias[col] : 0.f;
+      BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
+      if (ev) ec = bn_eval_col(bn, col);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = row0 + kq * 4 + r;
         vals[nt][r] = bias ? (acc[nt][r] + bv0) : acc[nt][r];
+        if (ev) vals[nt][r] = bn_affine(vals[nt][r], ec.m, ec.rs, ec.g, ec.b, bn.ev_relu);
         if (col < Cres && row < n_rows) out[(size_t)row * Cres + col] = vals[nt][r];
       }
     }
@@ -482,6 +492,19 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
       (void)hipFuncSetAttribute((const void*)conv_apply_ws<1, TRANS_W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void)hipFuncSetAttribute((const void*)conv_apply_ws<2, TRANS_W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
+    if constexpr (!TRANS_W) {
+      if (bn.ev_mean) {   // eval-mode BatchNorm (+ ReLU) in the epilogue: the instances compiled for it
+        static BtcPerDeviceOnce once_ev;
+        btc_once_per_device(once_ev, [] {
+          (void)hipFuncSetAttribute((const void*)conv_apply_ws<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          (void)hipFuncSetAttribute((const void*)conv_apply_ws<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+        if (nt == 1) conv_apply_ws<1, false, true><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+        else conv_apply_ws<2, false, true><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+        BTC_LAUNCH_CHECK();
+        return BTC_OK;
+      }
+    }
     if (nt == 1) conv_apply_ws<1, TRANS_W><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
     else conv_apply_ws<2, TRANS_W><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
     BTC_LAUNCH_CHECK();

@@ -57,6 +57,42 @@ def conv_bn_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean,
     return x, y, stats
 
 
+def eval_fold_wanted(features, weight, bias, bn):
+    """conv -> bn (-> ReLU) as ONE launch (btc_conv_bn_eval_fwd: the transform in the conv kernel's epilogue, only y written)?  When, and
+    only when, bn reads its running statistics and nothing will ask for a gradient through the node -- eval mode WITH gradients
+    (frozen-statistics fine-tuning) keeps the autograd node, whose backward reads x.  BTC_TUNE_EVAL_FOLD (key 23) = 1: never.
+    Same rule as the compiled binding (binding.cpp eval_fold_wanted)."""
+    if bn.training or not bn.track_running_stats or bn.running_mean is None:
+        return False
+    if lib().btc_tune_value(23) == 1:
+        return False
+    if not torch.is_grad_enabled():
+        return True
+    return not any(t is not None and t.requires_grad for t in (features, weight, bias, bn.weight, bn.bias))
+
+
+def conv_bn_eval_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean, running_var, eps, relu):
+    """eval-mode conv -> BatchNorm (running statistics) -> [ReLU] in one launch; weights prepared as conv_bn_forward prepares them.  -> y"""
+    n, K = map_fwd.shape
+    cin, cout = w.shape[-2], w.shape[-1]
+    from . import ops
+    F = fast() if ops.PROFILE is None else None
+    if F is not None:
+        return F.conv_bn_eval_fold(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean, running_var, float(eps), bool(relu), stream_ptr())
+    if not (features.is_contiguous() and w.numel() == K * cin * cout and features.shape[1] == cin and running_mean.numel() == cout):
+        raise ValueError("conv_bn_eval_forward: weight / statistics do not match the rulebook / features")
+    y = torch.empty((n, cout), dtype=features.dtype, device=features.device)
+    operands = 1 if features.dtype == torch.bfloat16 else 0
+    if ops._bf16_operands(features, K, cin, cout):
+        operands, w = 2, ops._weights_bf16(w, K, cin, cout)[1]
+    elif ops._split_operands(features, K, cin, cout, n):
+        operands, w = 3, ops._weights_split(w, K, cin, cout)[1]
+    check(lib().btc_conv_bn_eval_fwd(operands, ptr(features), int(features.shape[0]), ptr(w), ptr(b), ptr(map_fwd), ptr(ord_fwd), n, K, cin, cout,
+                                     ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps), int(relu), ptr(y), stream_ptr()),
+          "btc_conv_bn_eval_fwd")
+    return y
+
+
 def bn_forward(x, weight, bias, running_mean, running_var, num_batches_tracked, use_batch, momentum, eps, relu):
     """y = [relu](batchnorm(x)); returns (y, stats) with stats (2, C) = mean | rstd.  Running statistics / num_batches_tracked
     are updated in the kernel when given (training)."""

@@ -949,6 +949,13 @@ def indice_conv_bn_relu(features, weight, bias, rulebook, bn, relu, inverse=Fals
     rv = bn.running_var if bn.track_running_stats else None
     maps = (rulebook.nbr_in, rulebook.nbr_out) if inverse else (rulebook.nbr_out, rulebook.map_bwd)
     ords = (rulebook.order_in, rulebook.order_out) if inverse else (rulebook.order_out, rulebook.order_in)
+    if PROFILE is None and CAPTURE is None and features.is_cuda and maps[0].shape[0] >= 1:
+        from . import fused_bn
+        if fused_bn.eval_fold_wanted(features, weight, bias, bn):
+            # eval-mode BatchNorm and no gradient asked for: one launch, the transform in the conv's epilogue (either binding)
+            with torch.no_grad():
+                return fused_bn.conv_bn_eval_forward(_actc(features), _f32c(weight), _f32c(bias) if bias is not None else None, maps[0], ords[0],
+                                                     bn.weight, bn.bias, rm, rv, bn.eps, relu)
     F = fast() if (PROFILE is None and CAPTURE is None and NATIVE_AUTOGRAD) else None
     if F is not None and features.is_cuda:
         # C++ autograd node (csrc/binding.cpp ConvBNReLUNode): same launches, no Python Function.apply / ctx bookkeeping

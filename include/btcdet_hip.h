@@ -73,6 +73,7 @@ int btc_version(void);
 #define BTC_TUNE_RB_MARK_MULTI 19 /* chain rulebooks: 1 = mark every level by its own launch (rb_mark / rb_mark_b) instead of one launch for the leading run of strided conv layers (cross-check: same levels) */
 #define BTC_TUNE_SPLIT_PAIR 21 /* split-operand kernel and bf16-operand kernel, 32-channel reductions: 0 = built-in policy, 1 = one offset per item, 2 = two offsets per 64-channel item wherever a tile shape has the instance (same bits) */
 #define BTC_TUNE_WGRAD_NARROW 22 /* weight gradient of a layer with <= 8 result channels walked over its input rows (conv_wgrad_n.hip; needs the backward map or nbr_in == nbr_out): 0 = where supported, 1 = never */
+#define BTC_TUNE_EVAL_FOLD 23 /* host bindings, conv -> BatchNorm (eval) -> ReLU without autograd: 0 = one launch, the transform in the conv epilogue (include/btcdet_hip_infer.h), 1 = never (conv, then the two BatchNorm launches); same bits */
 #define BTC_TUNE_APPLY_DEBUG 3 /* timing experiments only (WRONG results): 1 = no MFMA phase, 2 = no loads in the main loop */
 int btc_tune_set(int key, int value);
 int btc_tune_value(int key);   /* current value of a key (0 = built-in policy) */
