@@ -184,6 +184,9 @@ EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 # the entry points of the second public header, include/btcdet_hip_infer.h (same library, same rules)
 _INFER_SIGS = {
     "btc_conv_bn_eval_fwd": (ci, [ci, vp, ctypes.c_longlong, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]),
+    "btc_det_select_nms_ws_bytes": (sz, [ci, ci]),
+    "btc_det_select_nms": (ci, [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "btc_det_finish": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, ci, ci, c_f32p, ci, vp, vp, vp, vp, vp, vp]),
 }
 
 INFER_EXPORTED_SYMBOLS = tuple(_INFER_SIGS.keys())
