@@ -47,6 +47,9 @@ inline const int32_t* ip(int64_t p) { return reinterpret_cast<const int32_t*>(p)
 inline void need(bool ok, const char* msg) {
   if (!ok) throw std::runtime_error(msg);
 }
+inline void need(bool ok, const char* who, const char* msg) {   // (the text is put together on failure only)
+  if (!ok) throw std::runtime_error(std::string(who) + msg);
+}
 
 // bf16 copies of a layer's weights for the bf16-operand kernels (btc_conv_*_bf16w): row 0 = W [K][Cin][Cout] (dgrad operand),
 // row 1 = W^T [K][Cout][Cin] (forward operand).  Converted when first needed after the parameter changed (its version counter
@@ -61,12 +64,6 @@ struct WqEntry {
 };
 std::mutex g_wq_mu;
 std::unordered_map<const void*, WqEntry> g_wq;
-
-bool bf16_operands(const Tensor& features, int64_t K, int64_t cred, int64_t cres) {
-  return features.scalar_type() == at::kBFloat16 && btc_conv_bf16w_supported((int)K, (int)cred, (int)cres) &&
-         btc_tune_value(BTC_TUNE_BF16_OPERANDS) != 1;
-}
-
 // planes = 1: the bf16 copies; planes = 3: the hi / mid / lo planes of the split-operand kernel (btc_weights_split3) -- same rows
 std::unordered_map<const void*, WqEntry> g_ws;
 
@@ -100,8 +97,6 @@ Tensor weights_q(const Tensor& w, int64_t K, int64_t cin, int64_t cout, int64_t 
   for (auto e = tab.begin(); e != tab.end();) e = e->second.weak.expired() ? tab.erase(e) : std::next(e);
   return q;
 }
-
-Tensor weights_bf16(const Tensor& w, int64_t K, int64_t cin, int64_t cout, int64_t stream) { return weights_q(w, K, cin, cout, stream, 1); }
 
 // the operand copies of MANY leaf weights in one launch (a parameter group's eligible layers right after its optimizer step, on the
 // stream its next forward runs on): every cache entry is brought to the weight's current version, later weights_q calls hit.
@@ -151,44 +146,68 @@ void ensure_scratch(const Tensor& like, int64_t stream) {
   tab.emplace(key, t);
 }
 
-// fp32 launch of n_rows rows on the split-operand kernel (csrc/conv_apply_split.hip)?  The library's policy; BTC_TUNE_SPLIT = 1: never
-bool split_operands(const Tensor& src, int64_t K, int64_t cred, int64_t cres, int64_t n_rows, int64_t stream) {
-  if (!(src.scalar_type() == at::kFloat && btc_conv_split_wanted((int)K, (int)cred, (int)cres, (int)n_rows))) return false;
-  if (src.numel() * 4 >= (int64_t)0xFFFFFF00LL) return false;   // the kernel's gathers use 32-bit byte offsets (the C entry refuses past them): exact kernels
-  ensure_scratch(src, stream);
-  return true;
+// The operands of ONE apply launch (forward or dgrad): which kind (BTC_OPERANDS_*), the weight operand that goes with it, and the tensor that
+// keeps that operand alive.  The only place that knows the policy:
+//   bf16 src  : a bf16 copy of the weights on the bf16 matrix pipe where the kernel takes the shape (BTC_TUNE_BF16_OPERANDS = 1: never),
+//               fp32 weights otherwise;
+//   fp32 src  : the hi / mid / lo planes on the split-operand kernel (csrc/conv_apply_split.hip) where the library wants it
+//               (btc_conv_split_wanted; BTC_TUNE_SPLIT = 1: never) and its 32-bit byte offsets reach all of src (the C entry refuses past
+//               4 GB), with the stream's scratch buffer registered for its z-split launches; the exact fp32 kernels otherwise.
+// Row 0 of a converted copy is W [K][Cin][Cout] (dgrad operand), row 1 = W^T [K][Cout][Cin] (forward operand).
+struct Operands {
+  int operands;
+  const void* w;
+  Tensor hold;
+};
+
+Operands operands_of(const Tensor& src, const Tensor& w, int64_t K, int64_t cred, int64_t cres, int64_t n_rows, int pass, int64_t stream) {
+  const bool fwd = pass == BTC_PASS_FWD, bf = src.scalar_type() == at::kBFloat16;
+  int planes = 0;
+  if (bf) {
+    if (btc_conv_bf16w_supported((int)K, (int)cred, (int)cres) && btc_tune_value(BTC_TUNE_BF16_OPERANDS) != 1) planes = 1;
+  } else if (src.scalar_type() == at::kFloat && btc_conv_split_wanted((int)K, (int)cred, (int)cres, (int)n_rows) &&
+             src.numel() * 4 < (int64_t)0xFFFFFF00LL) {
+    ensure_scratch(src, stream);
+    planes = 3;
+  }
+  if (!planes) return {bf ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32, w.data_ptr(), Tensor()};
+  Tensor q = weights_q(w, K, fwd ? cred : cres, fwd ? cres : cred, stream, planes);
+  return {planes == 1 ? BTC_OPERANDS_BF16 : BTC_OPERANDS_F32_SPLIT, (const char*)q.data_ptr() + (fwd ? 2 * planes * w.numel() : 0), q};
 }
 
 // out = conv(features) ; features (n_src, Cin) fp32 | bf16 contiguous, w [K.., Cin, Cout] fp32, map_fwd (n_res, K) int32
 // a row-order hint of a map (csrc/row_order.hip): int32 (n_rows,), or nothing
-const int32_t* order_ptr(const OptTensor& o, int64_t n_rows, const char* what) {
+const int32_t* order_ptr(const OptTensor& o, int64_t n_rows, const char* who) {
   if (!o.has_value() || !o->defined()) return nullptr;
-  need(o->scalar_type() == at::kInt && o->is_contiguous() && o->numel() == n_rows, what);
+  need(o->scalar_type() == at::kInt && o->is_contiguous() && o->numel() == n_rows, who, ": the row order does not match the map");
   return (const int32_t*)o->data_ptr();
 }
 
+// what the three forward sites share: the checks of (features, w, map_fwd), the row-order hint and the result tensor
+struct FwdSite {
+  int64_t cin, cout, K, n_res;
+  const int32_t* order;
+  Tensor out;
+};
+
+// stats_ok: the eval fold's check of its running statistics, reported where it always was (behind the shapes, before the row order)
+FwdSite fwd_site(const char* who, const Tensor& features, const Tensor& w, const Tensor& map_fwd, const OptTensor& order_fwd, bool stats_ok = true) {
+  FwdSite f;
+  f.cin = w.size(-2), f.cout = w.size(-1), f.K = map_fwd.size(1), f.n_res = map_fwd.size(0);
+  need(features.is_contiguous() && w.is_contiguous() && map_fwd.is_contiguous(), who, ": contiguous tensors expected");
+  need(w.numel() == f.K * f.cin * f.cout && features.size(1) == f.cin, who, ": weight does not match the rulebook / features");
+  need(stats_ok, who, ": running statistics of the result channels expected");
+  f.order = order_ptr(order_fwd, f.n_res, who);
+  f.out = at::empty({f.n_res, f.cout}, features.options());
+  return f;
+}
+
 Tensor conv_fwd(const Tensor& features, const Tensor& w, const OptTensor& bias, const Tensor& map_fwd, const OptTensor& order_fwd, int64_t stream) {
-  const int64_t cin = w.size(-2), cout = w.size(-1), K = map_fwd.size(1), n_res = map_fwd.size(0);
-  need(features.is_contiguous() && w.is_contiguous() && map_fwd.is_contiguous(), "conv_fwd: contiguous tensors expected");
-  need(w.numel() == K * cin * cout && features.size(1) == cin, "conv_fwd: weight does not match the rulebook / features");
-  const int32_t* order = order_ptr(order_fwd, n_res, "conv_fwd: the row order does not match the map");
-  Tensor out = at::empty({n_res, cout}, features.options());
-  if (bf16_operands(features, K, cin, cout)) {
-    Tensor q = weights_bf16(w, K, cin, cout, stream);
-    chk(btc_conv_apply_ordered(BTC_PASS_FWD, BTC_OPERANDS_BF16, features.data_ptr(), (const char*)q.data_ptr() + 2 * w.numel(), fptr(bias),
-                               (const int32_t*)map_fwd.data_ptr(), order, (int)n_res, (int)K, (int)cin, (int)cout, out.data_ptr(), st(stream)),
-        "btc_conv_apply_ordered (fwd, bf16 operands)");
-  } else if (split_operands(features, K, cin, cout, n_res, stream)) {
-    Tensor q = weights_q(w, K, cin, cout, stream, 3);
-    chk(btc_conv_apply_src(BTC_PASS_FWD, BTC_OPERANDS_F32_SPLIT, features.data_ptr(), (long long)features.size(0), (const char*)q.data_ptr() + 6 * w.numel(), fptr(bias),
-                               (const int32_t*)map_fwd.data_ptr(), order, (int)n_res, (int)K, (int)cin, (int)cout, out.data_ptr(), st(stream)),
-        "btc_conv_apply_src (fwd, split operands)");
-  } else {
-    const int operands = features.scalar_type() == at::kBFloat16 ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32;
-    chk(btc_conv_apply_ordered(BTC_PASS_FWD, operands, features.data_ptr(), w.data_ptr(), fptr(bias), (const int32_t*)map_fwd.data_ptr(), order,
-                               (int)n_res, (int)K, (int)cin, (int)cout, out.data_ptr(), st(stream)), "btc_conv_apply_ordered (fwd)");
-  }
-  return out;
+  FwdSite f = fwd_site("conv_fwd", features, w, map_fwd, order_fwd);
+  const Operands op = operands_of(features, w, f.K, f.cin, f.cout, f.n_res, BTC_PASS_FWD, stream);
+  chk(btc_conv_apply_src(BTC_PASS_FWD, op.operands, features.data_ptr(), (long long)features.size(0), op.w, fptr(bias), (const int32_t*)map_fwd.data_ptr(),
+                         f.order, (int)f.n_res, (int)f.K, (int)f.cin, (int)f.cout, f.out.data_ptr(), st(stream)), "btc_conv_apply_src (fwd)");
+  return f.out;
 }
 
 // y = [relu](batchnorm(x)); stats (2, C) = mean | rstd
@@ -230,35 +249,20 @@ std::tuple<Tensor, Tensor, Tensor> conv_bn_fwd(const Tensor& features, const Ten
                                                const OptTensor& order_fwd, const OptTensor& gamma, const OptTensor& beta, const OptTensor& rm, const OptTensor& rv,
                                                const OptTensor& nbt, bool use_batch, double momentum, double eps, bool relu, const Tensor& ws,
                                                int64_t ws_bytes, int64_t stream) {
-  const int64_t cin = w.size(-2), cout = w.size(-1), K = map_fwd.size(1), n_res = map_fwd.size(0);
-  if (use_batch && n_res >= 1) {
-    // training-mode BatchNorm: its batch statistics come out of the conv kernel's epilogue (btc_conv_bn_relu_fwd, csrc/bn_fuse.h)
-    need(features.is_contiguous() && w.is_contiguous() && map_fwd.is_contiguous(), "conv_bn_fwd: contiguous tensors expected");
-    need(w.numel() == K * cin * cout && features.size(1) == cin, "conv_bn_fwd: weight does not match the rulebook / features");
-    const int32_t* order = order_ptr(order_fwd, n_res, "conv_bn_fwd: the row order does not match the map");
-    Tensor x = at::empty({n_res, cout}, features.options());
-    Tensor y = at::empty_like(x);
-    Tensor stats = at::empty({2, cout}, features.options().dtype(at::kFloat));
+  if (use_batch && map_fwd.size(0) >= 1) {
+    // training-mode BatchNorm: its batch statistics come out of the conv kernel's epilogue (btc_conv_bn_relu_fwd_src, csrc/bn_fuse.h)
+    FwdSite f = fwd_site("conv_bn_fwd", features, w, map_fwd, order_fwd);
+    Tensor y = at::empty_like(f.out);
+    Tensor stats = at::empty({2, f.cout}, features.options().dtype(at::kFloat));
     Tensor fw = fuse_ws_of(features, stream);
     float* mean = (float*)stats.data_ptr();
     long long* nb = (nbt.has_value() && nbt->defined()) ? (long long*)nbt->data_ptr() : nullptr;
-    int operands = features.scalar_type() == at::kBFloat16 ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32;
-    const void* wp = w.data_ptr();
-    Tensor q;
-    if (bf16_operands(features, K, cin, cout)) {          // (round 5: the bf16-operand kernel gathers the statistics too)
-      q = weights_bf16(w, K, cin, cout, stream);
-      operands = BTC_OPERANDS_BF16;
-      wp = (const char*)q.data_ptr() + 2 * w.numel();
-    } else if (split_operands(features, K, cin, cout, n_res, stream)) {
-      q = weights_q(w, K, cin, cout, stream, 3);
-      operands = BTC_OPERANDS_F32_SPLIT;
-      wp = (const char*)q.data_ptr() + 6 * w.numel();
-    }
-    chk(btc_conv_bn_relu_fwd_src(operands, features.data_ptr(), (long long)features.size(0), wp, fptr(bias), (const int32_t*)map_fwd.data_ptr(), order, (int)n_res, (int)K,
-                             (int)cin, (int)cout, x.data_ptr(), fptr(gamma), fptr(beta), (float*)vptr(rm), (float*)vptr(rv), nb, (float)momentum,
-                             (float)eps, (int)relu, y.data_ptr(), mean, mean + cout, ws.data_ptr(), (size_t)ws_bytes, fw.data_ptr(), st(stream)),
-        "btc_conv_bn_relu_fwd");
-    return std::make_tuple(x, y, stats);
+    const Operands op = operands_of(features, w, f.K, f.cin, f.cout, f.n_res, BTC_PASS_FWD, stream);
+    chk(btc_conv_bn_relu_fwd_src(op.operands, features.data_ptr(), (long long)features.size(0), op.w, fptr(bias), (const int32_t*)map_fwd.data_ptr(), f.order,
+                                 (int)f.n_res, (int)f.K, (int)f.cin, (int)f.cout, f.out.data_ptr(), fptr(gamma), fptr(beta), (float*)vptr(rm), (float*)vptr(rv), nb,
+                                 (float)momentum, (float)eps, (int)relu, y.data_ptr(), mean, mean + f.cout, ws.data_ptr(), (size_t)ws_bytes, fw.data_ptr(), st(stream)),
+        "btc_conv_bn_relu_fwd_src");
+    return std::make_tuple(f.out, y, stats);
   }
   Tensor x = conv_fwd(features, w, bias, map_fwd, order_fwd, stream);
   auto ys = bn_fwd(x, gamma, beta, rm, rv, nbt, use_batch, momentum, eps, relu, ws, ws_bytes, stream);
@@ -266,35 +270,20 @@ std::tuple<Tensor, Tensor, Tensor> conv_bn_fwd(const Tensor& features, const Ten
 }
 
 // conv -> BatchNorm (eval: running statistics) -> ReLU of a forward pass nobody differentiates: ONE launch, the transform in the conv
-// kernel's epilogue (btc_conv_bn_eval_fwd, include/btcdet_hip_infer.h) -- no x, no statistics, no BatchNorm workspace.  Weights are
-// prepared as conv_bn_fwd prepares them (same policy functions), so the two routes pick the same kernel and give the same bits.
+// kernel's epilogue (btc_conv_bn_eval_fwd, include/btcdet_hip_infer.h) -- no x, no statistics, no BatchNorm workspace.  The operands come
+// from the same helper as conv_bn_fwd's, so the two routes pick the same kernel and give the same bits.
 std::atomic<int64_t> g_eval_fold_calls{0};
 
 Tensor conv_bn_eval_fold(const Tensor& features, const Tensor& w, const OptTensor& bias, const Tensor& map_fwd, const OptTensor& order_fwd,
                          const OptTensor& gamma, const OptTensor& beta, const Tensor& rm, const Tensor& rv, double eps, bool relu, int64_t stream) {
-  const int64_t cin = w.size(-2), cout = w.size(-1), K = map_fwd.size(1), n_res = map_fwd.size(0);
-  need(features.is_contiguous() && w.is_contiguous() && map_fwd.is_contiguous(), "conv_bn_eval_fold: contiguous tensors expected");
-  need(w.numel() == K * cin * cout && features.size(1) == cin, "conv_bn_eval_fold: weight does not match the rulebook / features");
-  need(rm.defined() && rv.defined() && rm.numel() == cout && rv.numel() == cout, "conv_bn_eval_fold: running statistics of the result channels expected");
-  const int32_t* order = order_ptr(order_fwd, n_res, "conv_bn_eval_fold: the row order does not match the map");
-  Tensor y = at::empty({n_res, cout}, features.options());
-  int operands = features.scalar_type() == at::kBFloat16 ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32;
-  const void* wp = w.data_ptr();
-  Tensor q;
-  if (bf16_operands(features, K, cin, cout)) {
-    q = weights_bf16(w, K, cin, cout, stream);
-    operands = BTC_OPERANDS_BF16;
-    wp = (const char*)q.data_ptr() + 2 * w.numel();
-  } else if (split_operands(features, K, cin, cout, n_res, stream)) {
-    q = weights_q(w, K, cin, cout, stream, 3);
-    operands = BTC_OPERANDS_F32_SPLIT;
-    wp = (const char*)q.data_ptr() + 6 * w.numel();
-  }
-  chk(btc_conv_bn_eval_fwd(operands, features.data_ptr(), (long long)features.size(0), wp, fptr(bias), (const int32_t*)map_fwd.data_ptr(), order,
-                           (int)n_res, (int)K, (int)cin, (int)cout, fptr(gamma), fptr(beta), (const float*)rm.data_ptr(), (const float*)rv.data_ptr(),
-                           (float)eps, (int)relu, y.data_ptr(), st(stream)), "btc_conv_bn_eval_fwd");
+  FwdSite f = fwd_site("conv_bn_eval_fold", features, w, map_fwd, order_fwd,
+                       rm.defined() && rv.defined() && rm.numel() == w.size(-1) && rv.numel() == w.size(-1));
+  const Operands op = operands_of(features, w, f.K, f.cin, f.cout, f.n_res, BTC_PASS_FWD, stream);
+  chk(btc_conv_bn_eval_fwd(op.operands, features.data_ptr(), (long long)features.size(0), op.w, fptr(bias), (const int32_t*)map_fwd.data_ptr(), f.order,
+                           (int)f.n_res, (int)f.K, (int)f.cin, (int)f.cout, fptr(gamma), fptr(beta), (const float*)rm.data_ptr(), (const float*)rv.data_ptr(),
+                           (float)eps, (int)relu, f.out.data_ptr(), st(stream)), "btc_conv_bn_eval_fwd");
   ++g_eval_fold_calls;
-  return y;
+  return f.out;
 }
 
 int64_t eval_fold_calls() { return g_eval_fold_calls.load(); }
@@ -454,7 +443,7 @@ std::tuple<OptTensor, OptTensor> conv_bwd(const Tensor& features, const Tensor& 
   const int64_t cin = w.size(-2), cout = w.size(-1), K = map_fwd.size(1), n_res = map_fwd.size(0), n_src = map_bwd.size(0);
   need(grad_out.is_contiguous() && grad_out.scalar_type() == features.scalar_type(), "conv_bwd: grad must be contiguous and of the activation type");
   const bool bf = features.scalar_type() == at::kBFloat16;
-  const int32_t* order = order_ptr(order_bwd, n_src, "conv_bwd: the row order does not match the map");
+  const int32_t* order = order_ptr(order_bwd, n_src, "conv_bwd");
   // a submanifold rulebook has ONE map: its backward map is the forward map with the offset index mirrored, and the caller hands
   // in the same tensor for both (ops.Rulebook.map_bwd) -- the dgrad kernels then read column K-1-k for offset k
   const bool mirror = map_fwd.numel() > 0 && map_bwd.data_ptr() == map_fwd.data_ptr();
@@ -489,18 +478,10 @@ std::tuple<OptTensor, OptTensor> conv_bwd(const Tensor& features, const Tensor& 
   auto run_dgrad = [&]() {
   if (need_din) {
     Tensor d = at::empty({n_src, cin}, features.options());
-    if (bf16_operands(grad_out, K, cout, cin)) {
-      Tensor q = q_hold = weights_bf16(w, K, cin, cout, stream);
-      chk(btc_conv_apply_ordered(pass_dgrad, BTC_OPERANDS_BF16, grad_out.data_ptr(), q.data_ptr(), nullptr, (const int32_t*)map_bwd.data_ptr(),
-                                 order, (int)n_src, (int)K, (int)cin, (int)cout, d.data_ptr(), st(stream)), "btc_conv_apply_ordered (dgrad, bf16 operands)");
-    } else if (split_operands(grad_out, K, cout, cin, n_src, stream)) {
-      Tensor q = q_hold = weights_q(w, K, cin, cout, stream, 3);
-      chk(btc_conv_apply_src(pass_dgrad, BTC_OPERANDS_F32_SPLIT, grad_out.data_ptr(), (long long)grad_out.size(0), q.data_ptr(), nullptr, (const int32_t*)map_bwd.data_ptr(),
-                                 order, (int)n_src, (int)K, (int)cin, (int)cout, d.data_ptr(), st(stream)), "btc_conv_apply_src (dgrad, split operands)");
-    } else
-      chk(btc_conv_apply_ordered(pass_dgrad, bf ? BTC_OPERANDS_BF16_ACT : BTC_OPERANDS_F32, grad_out.data_ptr(), w.data_ptr(), nullptr,
-                                 (const int32_t*)map_bwd.data_ptr(), order, (int)n_src, (int)K, (int)cin, (int)cout, d.data_ptr(), st(stream)),
-          "btc_conv_apply_ordered (dgrad)");
+    const Operands op = operands_of(grad_out, w, K, cout, cin, n_src, pass_dgrad, stream);
+    q_hold = op.hold;
+    chk(btc_conv_apply_src(pass_dgrad, op.operands, grad_out.data_ptr(), (long long)grad_out.size(0), op.w, nullptr, (const int32_t*)map_bwd.data_ptr(), order,
+                           (int)n_src, (int)K, (int)cin, (int)cout, d.data_ptr(), st(stream)), "btc_conv_apply_src (dgrad)");
     din = d;
   }
   };

@@ -585,25 +585,23 @@ extern "C" int btc_conv_bn_relu_fwd_src(int operands, const void* src, long long
   BTC_CHECK_ARG(n_rows >= 1, "btc_conv_bn_relu_fwd: empty input");
   BTC_CHECK_ARG(operands >= BTC_OPERANDS_F32 && operands <= BTC_OPERANDS_F32_SPLIT, "btc_conv_bn_relu_fwd: operands=%d", operands);
   const bool bf = operands == BTC_OPERANDS_BF16_ACT || operands == BTC_OPERANDS_BF16;
-  int fused = 0;
-  if (fuse_ws && Cout <= BN_FUSE_CMAX && btc_tune_get(BTC_TUNE_BN_FUSE) != 1) {
-    BnFuse bn = btc_bn_fuse_none();   // (statistics mode: the eval-mode fields stay null)
+  const bool fused = fuse_ws && Cout <= BN_FUSE_CMAX && btc_tune_get(BTC_TUNE_BN_FUSE) != 1;
+  BnFuse bn = btc_bn_fuse_none();   // (statistics mode: the eval-mode fields stay null)
+  if (fused) {
     bn.counter = (int32_t*)fuse_ws;
     bn.slots = (double*)((char*)fuse_ws + 256);
     bn.mean_out = save_mean; bn.rstd_out = save_rstd;
     bn.running_mean = running_mean; bn.running_var = running_var; bn.num_batches = num_batches_tracked;
     bn.momentum = momentum; bn.eps = eps; bn.N = n_rows; bn.C = Cout; bn.nslots = btc_bn_fuse_nslots(n_rows);
-    int rc = btc_conv_fwd_stats(operands, src, src_rows, (const float*)W, bias, nbr, order, n_rows, K, Cin, Cout, x, bn, (hipStream_t)stream, &fused);
-    if (rc) return rc;
-  } else {
-    int rc = btc_conv_apply_src(BTC_PASS_FWD, operands, src, src_rows, W, bias, nbr, order, n_rows, K, Cin, Cout, x, stream);
-    if (rc) return rc;
   }
+  const int rc = btc_apply("btc_conv_bn_relu_fwd_src", BTC_PASS_FWD, operands, src, src_rows, W, bias, nbr, order, n_rows, K, Cin, Cout, x,
+                           (hipStream_t)stream, fused ? &bn : nullptr);
+  if (rc) return rc;
   if (bf)
     return bn_fwd_impl<true>((const float*)x, n_rows, Cout, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, 1, relu,
-                             (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused != 0);
+                             (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused);
   return bn_fwd_impl<false>((const float*)x, n_rows, Cout, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, 1, relu,
-                            (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused != 0);
+                            (float*)y, save_mean, save_rstd, ws, ws_bytes, stream, fused);
 }
 
 // ---- conv -> BatchNorm (eval: running statistics) -> ReLU in ONE launch: the affine and the ReLU in the conv's epilogue, only y is written
@@ -618,6 +616,5 @@ extern "C" int btc_conv_bn_eval_fwd(int operands, const void* src, long long src
   BnFuse bn = btc_bn_fuse_none();
   bn.ev_mean = running_mean; bn.ev_var = running_var; bn.ev_gamma = gamma; bn.ev_beta = beta; bn.ev_relu = relu ? 1 : 0;
   bn.eps = eps; bn.N = n_rows; bn.C = Cout;
-  int fused = 0;
-  return btc_conv_fwd_stats(operands, src, src_rows, (const float*)W, bias, nbr, order, n_rows, K, Cin, Cout, y, bn, (hipStream_t)stream, &fused);
+  return btc_apply("btc_conv_bn_eval_fwd", BTC_PASS_FWD, operands, src, src_rows, W, bias, nbr, order, n_rows, K, Cin, Cout, y, (hipStream_t)stream, &bn);
 }

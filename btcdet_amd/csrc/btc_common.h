@@ -80,9 +80,10 @@ int btc_launch_apply_glds(bool trans_w, int shape, int kc, int xcd, bool bf, con
                           const int32_t* nbr, const int32_t* order /* row order hint or NULL */, int n_rows, int K, int Cred, int Cres, void* out,
                           hipStream_t stream, const struct BnFuse* bn = nullptr /* bn_fuse.h: batch statistics of the result in the epilogue */);
 
-// sparse_conv.hip: forward conv + batch statistics of its result in the epilogue (bn_fuse.h), fp32 weights
-int btc_conv_fwd_stats(int operands, const void* src, long long src_rows, const float* W, const float* bias, const int32_t* nbr, const int32_t* order,
-                       int n_rows, int K, int Cin, int Cout, void* dst, const struct BnFuse& bn, hipStream_t stream, int* fused);
+// sparse_conv.hip: the one dispatcher from (pass, operands) to a kernel family behind every extern "C" apply entry point; bn = the
+// epilogue of a forward pass (bn_fuse.h: batch statistics, or the eval-mode BatchNorm) or NULL
+int btc_apply(const char* who, int pass, int operands, const void* src, long long src_rows, const void* W, const float* bias, const int32_t* nbr,
+              const int32_t* order, int n_rows, int K, int Cin, int Cout, void* dst, hipStream_t stream, const struct BnFuse* bn);
 
 // conv_apply_bf16.hip: bf16 operands on the bf16 matrix pipe; Wq[k][Cres][Cred] bf16
 int btc_apply_bf16w(const void* src, const void* Wq, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,

@@ -349,17 +349,3 @@ extern "C" int btc_weights_to_bf16(const float* W, int K, int Cin, int Cout, voi
   BTC_LAUNCH_CHECK();
   return BTC_OK;
 }
-
-extern "C" int btc_conv_fwd_bf16w(const void* feat, const void* wt_bf16, const float* bias, const int32_t* nbr_out, int n_out, int K, int Cin,
-                                  int Cout, void* out, void* stream) {
-  BTC_CHECK_ARG(n_out >= 0 && btc_conv_bf16w_supported(K, Cin, Cout), "btc_conv_fwd_bf16w: needs K <= 64, Cin %% 32 == 0, Cout %% 16 == 0 (K=%d, %d -> %d)",
-                K, Cin, Cout);
-  return apply_b(feat, wt_bf16, bias, nbr_out, nullptr, n_out, K, /*Cred=*/Cin, /*Cres=*/Cout, out, (hipStream_t)stream);
-}
-
-extern "C" int btc_conv_dgrad_bf16w(const void* dout, const void* w_bf16, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout, void* din,
-                                    void* stream) {
-  BTC_CHECK_ARG(n_in >= 0 && btc_conv_bf16w_supported(K, Cout, Cin), "btc_conv_dgrad_bf16w: needs K <= 64, Cout %% 32 == 0, Cin %% 16 == 0 (K=%d, %d -> %d)",
-                K, Cin, Cout);
-  return apply_b(dout, w_bf16, nullptr, nbr_in, nullptr, n_in, K, /*Cred=*/Cout, /*Cres=*/Cin, din, (hipStream_t)stream);
-}

@@ -533,105 +533,111 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
   return BTC_OK;
 }
 
-}  // namespace
-
-extern "C" int btc_conv_fwd(const float* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
-                            int Cin, int Cout, float* out, void* stream) {
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_fwd: bad sizes");
-  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_fwd: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
-  return launch_apply<false>(feat, W, bias, nbr_out, n_out, K, Cin, Cout, out, (hipStream_t)stream);
-}
-
-extern "C" int btc_conv_fwd_bf16(const void* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
-                                 int Cin, int Cout, void* out, void* stream) {
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_out >= 0, "btc_conv_fwd_bf16: bad sizes");
-  return launch_apply<false>((const float*)feat, W, bias, nbr_out, n_out, K, Cin, Cout, (float*)out, (hipStream_t)stream, true);
-}
-
-extern "C" int btc_conv_dgrad_bf16(const void* dout, const float* W, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
-                                   void* din, void* stream) {
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_in >= 0, "btc_conv_dgrad_bf16: bad sizes");
-  return launch_apply<true>((const float*)dout, W, nullptr, nbr_in, n_in, K, /*Cred=*/Cout, /*Cres=*/Cin, (float*)din,
-                            (hipStream_t)stream, true);
-}
-
-extern "C" int btc_conv_dgrad(const float* dout, const float* W, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
-                              float* din, void* stream) {
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_in >= 0, "btc_conv_dgrad: bad sizes");
-  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_dgrad: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
-  return launch_apply<true>(dout, W, nullptr, nbr_in, n_in, K, /*Cred=*/Cout, /*Cres=*/Cin, din, (hipStream_t)stream);
-}
-
 // split operands: the kernel gathers through 32-bit byte offsets -- the HOST refuses a source it cannot reach (or whose size it was not
 // told), nothing traps on the device
-static int split_source_ok(const char* who, long long src_rows, int Cred) {
+int split_source_ok(const char* who, long long src_rows, int Cred) {
   BTC_CHECK_ARG(src_rows >= 0, "%s: BTC_OPERANDS_F32_SPLIT needs the row count of src (btc_conv_apply_src / btc_conv_bn_relu_fwd_src)", who);
   BTC_CHECK_ARG(src_rows * Cred * 4 < 0xFFFFFF00LL, "%s: a source of %lld rows x %d channels is past the 32-bit gather offsets of the split-operand "
                 "kernel (4 GB): use BTC_OPERANDS_F32", who, src_rows, Cred);
   return BTC_OK;
 }
 
+}  // namespace
+
+// The ONE way from (pass, operands) to a kernel family: every extern "C" apply entry point, here and in bn.hip, is a wrapper over it and
+// holds only the checks that are its own.  who: the entry point, for the error texts.  src_rows: rows of src (read for split operands
+// only; < 0 = not told).  bn: the epilogue of a forward pass -- batch statistics or the eval-mode BatchNorm (bn_fuse.h) -- or NULL.
+int btc_apply(const char* who, int pass, int operands, const void* src, long long src_rows, const void* W, const float* bias, const int32_t* nbr,
+              const int32_t* order, int n_rows, int K, int Cin, int Cout, void* dst, hipStream_t stream, const BnFuse* bn) {
+  BTC_CHECK_ARG((pass == BTC_PASS_FWD || pass == BTC_PASS_DGRAD || pass == BTC_PASS_DGRAD_MIRROR) && operands >= BTC_OPERANDS_F32 &&
+                    operands <= BTC_OPERANDS_F32_SPLIT, "%s: pass=%d operands=%d", who, pass, operands);
+  // BTC_PASS_DGRAD_MIRROR: dgrad of a submanifold layer through its FORWARD map -- nbr_in[j][k] == nbr_out[j][K-1-k] there, so the
+  // kernels read column K-1-k for offset k and the backward map never exists (same bits as the explicit map: tests)
+  const int mirror = pass == BTC_PASS_DGRAD_MIRROR;
+  const bool fwd = pass == BTC_PASS_FWD;
+  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "%s: K=%d offsets, more than BTC_CONV_K_MAX = %d", who, K, BTC_CONV_K_MAX);
+  // (the entry points that take pass and operands report sizes HERE, behind K; the fixed-operand wrappers below repeat the check in front)
+  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "%s: bad sizes", who);
+  BTC_CHECK_ARG(fwd || bias == nullptr, "%s: dgrad takes no bias", who);
+  BTC_CHECK_ARG(!bn || Cout <= BN_FUSE_CMAX, "%s: more than %d channels", who, BN_FUSE_CMAX);
+  const int Cred = fwd ? Cin : Cout, Cres = fwd ? Cout : Cin;
+  if (operands == BTC_OPERANDS_BF16) {   // W = the bf16 copy of btc_weights_to_bf16 for this pass
+    const bool ok = btc_conv_bf16w_supported(K, Cred, Cres);
+    // (error texts are part of the entry points' contract: the BatchNorm ones word this refusal in Cin / Cout, without the values)
+    if (bn) BTC_CHECK_ARG(ok, "%s: bf16 operands need K <= 64, Cin %% 32 == 0, Cout %% 16 == 0", who);
+    else BTC_CHECK_ARG(ok, "%s: bf16 operands need K <= 64, Cred %% 32 == 0, Cres %% 16 == 0 (K=%d, %d -> %d)", who, K, Cin, Cout);
+    return btc_apply_bf16w(src, W, bias, nbr, order, n_rows, K, Cred, Cres, dst, stream, mirror, bn);
+  }
+  if (operands == BTC_OPERANDS_F32_SPLIT) {
+    if (n_rows > 0) {
+      const int rc = split_source_ok(who, src_rows, Cred);
+      if (rc) return rc;
+    }
+    return btc_apply_split((const float*)src, W, bias, nbr, order, n_rows, K, Cred, Cres, (float*)dst, stream, mirror, bn);
+  }
+  const bool bf = operands == BTC_OPERANDS_BF16_ACT;
+  if (fwd) return launch_apply<false>((const float*)src, (const float*)W, bias, nbr, n_rows, K, Cred, Cres, (float*)dst, stream, bf, order, 0, bn);
+  return launch_apply<true>((const float*)src, (const float*)W, nullptr, nbr, n_rows, K, Cred, Cres, (float*)dst, stream, bf, order, mirror, bn);
+}
+
+// The fixed-operand entry points.  Theirs alone: "bad sizes" is reported before a K past BTC_CONV_K_MAX, and for the two bf16 pairs a call
+// without rows is done once its own check has passed, whatever K and the channel counts are.
+#define BTC_SIZES_OK(who, n) BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && (n) >= 0, who ": bad sizes")
+
+extern "C" int btc_conv_fwd(const float* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
+                            int Cin, int Cout, float* out, void* stream) {
+  BTC_SIZES_OK("btc_conv_fwd", n_out);
+  return btc_apply("btc_conv_fwd", BTC_PASS_FWD, BTC_OPERANDS_F32, feat, -1LL, W, bias, nbr_out, nullptr, n_out, K, Cin, Cout, out, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int btc_conv_dgrad(const float* dout, const float* W, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
+                              float* din, void* stream) {
+  BTC_SIZES_OK("btc_conv_dgrad", n_in);
+  return btc_apply("btc_conv_dgrad", BTC_PASS_DGRAD, BTC_OPERANDS_F32, dout, -1LL, W, nullptr, nbr_in, nullptr, n_in, K, Cin, Cout, din, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int btc_conv_fwd_bf16(const void* feat, const float* W, const float* bias, const int32_t* nbr_out, int n_out, int K,
+                                 int Cin, int Cout, void* out, void* stream) {
+  BTC_SIZES_OK("btc_conv_fwd_bf16", n_out);
+  if (n_out == 0) return BTC_OK;
+  return btc_apply("btc_conv_fwd_bf16", BTC_PASS_FWD, BTC_OPERANDS_BF16_ACT, feat, -1LL, W, bias, nbr_out, nullptr, n_out, K, Cin, Cout, out, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int btc_conv_dgrad_bf16(const void* dout, const float* W, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout,
+                                   void* din, void* stream) {
+  BTC_SIZES_OK("btc_conv_dgrad_bf16", n_in);
+  if (n_in == 0) return BTC_OK;
+  return btc_apply("btc_conv_dgrad_bf16", BTC_PASS_DGRAD, BTC_OPERANDS_BF16_ACT, dout, -1LL, W, nullptr, nbr_in, nullptr, n_in, K, Cin, Cout, din, (hipStream_t)stream, nullptr);
+}
+#undef BTC_SIZES_OK
+
+// bf16 operands (W = a copy of btc_weights_to_bf16); their one combined refusal keeps its text
+extern "C" int btc_conv_fwd_bf16w(const void* feat, const void* wt_bf16, const float* bias, const int32_t* nbr_out, int n_out, int K, int Cin,
+                                  int Cout, void* out, void* stream) {
+  BTC_CHECK_ARG(n_out >= 0 && btc_conv_bf16w_supported(K, Cin, Cout), "btc_conv_fwd_bf16w: needs K <= 64, Cin %% 32 == 0, Cout %% 16 == 0 (K=%d, %d -> %d)",
+                K, Cin, Cout);
+  if (n_out == 0) return BTC_OK;
+  return btc_apply("btc_conv_fwd_bf16w", BTC_PASS_FWD, BTC_OPERANDS_BF16, feat, -1LL, wt_bf16, bias, nbr_out, nullptr, n_out, K, Cin, Cout, out, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int btc_conv_dgrad_bf16w(const void* dout, const void* w_bf16, const int32_t* nbr_in, int n_in, int K, int Cin, int Cout, void* din,
+                                    void* stream) {
+  BTC_CHECK_ARG(n_in >= 0 && btc_conv_bf16w_supported(K, Cout, Cin), "btc_conv_dgrad_bf16w: needs K <= 64, Cout %% 32 == 0, Cin %% 16 == 0 (K=%d, %d -> %d)",
+                K, Cin, Cout);
+  if (n_in == 0) return BTC_OK;
+  return btc_apply("btc_conv_dgrad_bf16w", BTC_PASS_DGRAD, BTC_OPERANDS_BF16, dout, -1LL, w_bf16, nullptr, nbr_in, nullptr, n_in, K, Cin, Cout, din, (hipStream_t)stream, nullptr);
+}
+
 extern "C" int btc_conv_apply_ordered(int pass, int operands, const void* src, const void* W, const float* bias, const int32_t* nbr,
                                       const int32_t* order, int n_rows, int K, int Cin, int Cout, void* dst, void* stream) {
   // (a submanifold layer's source has as many rows as its result; any other source's size is the caller's to state)
-  return btc_conv_apply_src(pass, operands, src, pass == BTC_PASS_DGRAD_MIRROR ? (long long)n_rows : -1LL, W, bias, nbr, order, n_rows, K, Cin, Cout,
-                            dst, stream);
+  return btc_apply("btc_conv_apply_ordered", pass, operands, src, pass == BTC_PASS_DGRAD_MIRROR ? (long long)n_rows : -1LL, W, bias, nbr, order, n_rows,
+                   K, Cin, Cout, dst, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int btc_conv_apply_src(int pass, int operands, const void* src, long long src_rows, const void* W, const float* bias, const int32_t* nbr,
                                   const int32_t* order, int n_rows, int K, int Cin, int Cout, void* dst, void* stream) {
-  BTC_CHECK_ARG((pass == BTC_PASS_FWD || pass == BTC_PASS_DGRAD || pass == BTC_PASS_DGRAD_MIRROR) && operands >= BTC_OPERANDS_F32 &&
-                    operands <= BTC_OPERANDS_F32_SPLIT, "btc_conv_apply_ordered: pass=%d operands=%d", pass, operands);
-  // BTC_PASS_DGRAD_MIRROR: dgrad of a submanifold layer through its FORWARD map -- nbr_in[j][k] == nbr_out[j][K-1-k] there, so the
-  // kernels read column K-1-k for offset k and the backward map never exists (same bits as the explicit map: tests)
-  const int mirror = pass == BTC_PASS_DGRAD_MIRROR;
-  if (mirror) pass = BTC_PASS_DGRAD;
-  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_apply_ordered: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_apply_ordered: bad sizes");
-  BTC_CHECK_ARG(pass == BTC_PASS_FWD || bias == nullptr, "btc_conv_apply_ordered: dgrad takes no bias");
-  const int Cred = pass == BTC_PASS_FWD ? Cin : Cout, Cres = pass == BTC_PASS_FWD ? Cout : Cin;
-  if (operands == BTC_OPERANDS_BF16) {
-    BTC_CHECK_ARG(btc_conv_bf16w_supported(K, Cred, Cres), "btc_conv_apply_ordered: bf16 operands need K <= 64, Cred %% 32 == 0, Cres %% 16 == 0 (K=%d, %d -> %d)",
-                  K, Cin, Cout);
-    return btc_apply_bf16w(src, W, bias, nbr, order, n_rows, K, Cred, Cres, dst, (hipStream_t)stream, mirror);
-  }
-  if (operands == BTC_OPERANDS_F32_SPLIT) {
-    if (n_rows > 0) {
-      const int rc = split_source_ok("btc_conv_apply_src", src_rows, Cred);
-      if (rc) return rc;
-    }
-    return btc_apply_split((const float*)src, W, bias, nbr, order, n_rows, K, Cred, Cres, (float*)dst, (hipStream_t)stream, mirror, nullptr);
-  }
-  const bool bf = operands == BTC_OPERANDS_BF16_ACT;
-  if (pass == BTC_PASS_FWD)
-    return launch_apply<false>((const float*)src, (const float*)W, bias, nbr, n_rows, K, Cred, Cres, (float*)dst, (hipStream_t)stream, bf, order);
-  return launch_apply<true>((const float*)src, (const float*)W, nullptr, nbr, n_rows, K, Cred, Cres, (float*)dst, (hipStream_t)stream, bf, order, mirror);
-}
-
-// forward conv whose epilogue also gathers the batch statistics of its result (bn_fuse.h); operands F32 / BF16_ACT only.
-// -> BTC_OK, *fused = 1 when the statistics were taken (always, for these operand kinds and n_rows > 0)
-int btc_conv_fwd_stats(int operands, const void* src, long long src_rows, const float* W, const float* bias, const int32_t* nbr, const int32_t* order,
-                       int n_rows, int K, int Cin, int Cout, void* dst, const BnFuse& bn, hipStream_t stream, int* fused) {
-  *fused = 0;
-  BTC_CHECK_ARG(K <= BTC_CONV_K_MAX, "btc_conv_bn_relu_fwd: K=%d offsets, more than BTC_CONV_K_MAX = %d", K, BTC_CONV_K_MAX);
-  BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1 && n_rows >= 0, "btc_conv_fwd_stats: bad sizes");
-  BTC_CHECK_ARG(operands >= BTC_OPERANDS_F32 && operands <= BTC_OPERANDS_F32_SPLIT, "btc_conv_fwd_stats: operands=%d", operands);
-  BTC_CHECK_ARG(Cout <= BN_FUSE_CMAX, "btc_conv_fwd_stats: more than %d channels", BN_FUSE_CMAX);
-  if (n_rows <= 0) return BTC_OK;
-  if (operands == BTC_OPERANDS_BF16) {   // W = wt_bf16 (the forward copy of btc_weights_to_bf16)
-    BTC_CHECK_ARG(btc_conv_bf16w_supported(K, Cin, Cout), "btc_conv_fwd_stats: bf16 operands need K <= 64, Cin %% 32 == 0, Cout %% 16 == 0");
-    *fused = 1;
-    return btc_apply_bf16w(src, W, bias, nbr, order, n_rows, K, Cin, Cout, dst, stream, 0, &bn);
-  }
-  if (operands == BTC_OPERANDS_F32_SPLIT) {
-    const int rc = split_source_ok("btc_conv_bn_relu_fwd_src", src_rows, Cin);
-    if (rc) return rc;
-    *fused = 1;
-    return btc_apply_split((const float*)src, W, bias, nbr, order, n_rows, K, Cin, Cout, (float*)dst, stream, 0, &bn);
-  }
-  const bool bf = operands == BTC_OPERANDS_BF16_ACT;
-  *fused = 1;
-  return launch_apply<false>((const float*)src, W, bias, nbr, n_rows, K, Cin, Cout, (float*)dst, stream, bf, order, 0, &bn);
+  return btc_apply("btc_conv_apply_src", pass, operands, src, src_rows, W, bias, nbr, order, n_rows, K, Cin, Cout, dst, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int btc_maxpool_fwd(const float* feat, const int32_t* nbr_out, int n_out, int K, int C, float* out, void* stream) {

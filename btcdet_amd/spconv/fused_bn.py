@@ -35,8 +35,8 @@ def fuse_ws(device):
 
 
 def conv_bn_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, relu):
-    """training-mode conv -> BatchNorm -> [ReLU] through btc_conv_bn_relu_fwd (statistics in the conv's epilogue); fp32 weights,
-    their split planes, or (bf16 features) their bf16 copy.
+    """training-mode conv -> BatchNorm -> [ReLU] through btc_conv_bn_relu_fwd (statistics in the conv's epilogue); the operands are
+    ops._operands' choice (fp32 weights, their split planes, or under bf16 features their bf16 copy).
     -> (x, y, stats (2, C) = mean | rstd)"""
     n, K = map_fwd.shape
     cin, cout = w.shape[-2], w.shape[-1]
@@ -44,12 +44,8 @@ def conv_bn_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean,
     y = torch.empty_like(x)
     stats = torch.empty((2, cout), dtype=torch.float32, device=features.device)
     ws, need = _ws(features.device, cout)
-    operands = 1 if features.dtype == torch.bfloat16 else 0
     from . import ops
-    if ops._bf16_operands(features, K, cin, cout):       # bf16-operand kernel: W = the forward (transposed) bf16 copy
-        operands, w = 2, ops._weights_bf16(w, K, cin, cout)[1]
-    elif ops._split_operands(features, K, cin, cout, n):   # split-operand kernel: W = the forward planes
-        operands, w = 3, ops._weights_split(w, K, cin, cout)[1]
+    operands, w = ops._operands(features, w, K, cin, cout, n, True)
     check(lib().btc_conv_bn_relu_fwd_src(operands, ptr(features), int(features.shape[0]), ptr(w), ptr(b), ptr(map_fwd), ptr(ord_fwd), n, K, cin, cout,
                                      ptr(x), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), float(momentum),
                                      float(eps), int(relu), ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(ws), need, ptr(fuse_ws(features.device)),
@@ -72,7 +68,7 @@ def eval_fold_wanted(features, weight, bias, bn):
 
 
 def conv_bn_eval_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_mean, running_var, eps, relu):
-    """eval-mode conv -> BatchNorm (running statistics) -> [ReLU] in one launch; weights prepared as conv_bn_forward prepares them.  -> y"""
+    """eval-mode conv -> BatchNorm (running statistics) -> [ReLU] in one launch; the operands come from the helper conv_bn_forward uses.  -> y"""
     n, K = map_fwd.shape
     cin, cout = w.shape[-2], w.shape[-1]
     from . import ops
@@ -82,11 +78,7 @@ def conv_bn_eval_forward(features, w, b, map_fwd, ord_fwd, gamma, beta, running_
     if not (features.is_contiguous() and w.numel() == K * cin * cout and features.shape[1] == cin and running_mean.numel() == cout):
         raise ValueError("conv_bn_eval_forward: weight / statistics do not match the rulebook / features")
     y = torch.empty((n, cout), dtype=features.dtype, device=features.device)
-    operands = 1 if features.dtype == torch.bfloat16 else 0
-    if ops._bf16_operands(features, K, cin, cout):
-        operands, w = 2, ops._weights_bf16(w, K, cin, cout)[1]
-    elif ops._split_operands(features, K, cin, cout, n):
-        operands, w = 3, ops._weights_split(w, K, cin, cout)[1]
+    operands, w = ops._operands(features, w, K, cin, cout, n, True)
     check(lib().btc_conv_bn_eval_fwd(operands, ptr(features), int(features.shape[0]), ptr(w), ptr(b), ptr(map_fwd), ptr(ord_fwd), n, K, cin, cout,
                                      ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps), int(relu), ptr(y), stream_ptr()),
           "btc_conv_bn_eval_fwd")

@@ -66,16 +66,18 @@ class _NoSpan(object):
 PROFILE = None  # set to a LaunchProfile() to instrument
 CAPTURE = None  # set to a list to record (features, weight, bias, map_fwd, map_bwd) of every sparse conv (tools/conv_bench.py)
 OVERLAP_WGRAD = True  # run wgrad on a side stream concurrently with dgrad (backward of every sparse conv)
-_SIDE = {}
+_STREAMS = {}
 
 
-def _side_stream(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SIDE.get(key)
+def _own_stream(kind, device):
+    """this module's stream of one kind per device: "wgrad" (beside dgrad) or "rulebook" (the count half of a strided rulebook)"""
+    key = (kind, device.index if device.index is not None else torch.cuda.current_device())
+    st = _STREAMS.get(key)
     if st is None:
-        st = torch.cuda.Stream(device=device)
-        _SIDE[key] = st
+        st = _STREAMS[key] = torch.cuda.Stream(device=device)
     return st
+
+
 _NOSPAN = _NoSpan()
 
 
@@ -353,19 +355,7 @@ def lookahead_enabled():
     return fast() is not None
 
 
-_RB_STREAM = {}
 _PIN = {}
-
-
-def _rb_stream(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    st = _RB_STREAM.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _RB_STREAM[key] = st
-    return st
-
-
 _PIN_LOCK = threading.Lock()
 
 
@@ -461,7 +451,7 @@ def prefetch_conv_rulebook(indices, batch_size, spatial_shape, ksize, stride=1, 
     if F is not None:
         h = F.rulebook_conv_start(indices, int(batch_size), g.a_in, g.a_out, g.a_k, g.a_s, g.a_p, g.a_d, g.mode, g.K, _conv_ws_bytes(g, batch_size))
         return _NativePending(F, h, indices, g)
-    return _start_conv_rulebook(indices, batch_size, g, _rb_stream(indices.device))
+    return _start_conv_rulebook(indices, batch_size, g, _own_stream("rulebook", indices.device))
 
 
 def get_indice_pairs(indices, batch_size, spatial_shape, ksize=3, stride=1, padding=0, dilation=1, out_padding=0,
@@ -536,65 +526,52 @@ def _overlap_ok(n_res):
     return OVERLAP_WGRAD and OVERLAP_MIN_ROWS <= n_res < OVERLAP_MAX_ROWS
 
 
-_WQ = {}
+_WQ = {}        # (id(w), planes) -> (weak reference, version, copy)
+_SCRATCH = {}   # (device index, stream) -> the stream's 48 MB scratch buffer for z-split launches (btc_set_scratch)
 
 
-def _bf16_operands(features, K, cred, cres):
-    """bf16 activations + a bf16 copy of the weights on the bf16 matrix pipe (csrc/conv_apply_bf16.hip) unless the tuning key
-    BTC_TUNE_BF16_OPERANDS is 1; same policy as the compiled binding (binding.cpp bf16_operands)"""
-    L = lib()
-    return features.dtype == torch.bfloat16 and L.btc_conv_bf16w_supported(int(K), int(cred), int(cres)) == 1 and L.btc_tune_value(8) != 1
-
-
-def _weights_bf16(w, K, cin, cout):
-    """(2, numel) bf16: row 0 = W [K][Cin][Cout], row 1 = W^T [K][Cout][Cin]; rebuilt when the parameter's version counter moved"""
+def _weights_q(w, K, cin, cout, planes):
+    """(2, planes * numel) bf16 operand copy of a weight: planes = 1 the bf16 copy, planes = 3 the hi | mid | lo planes of the split-operand
+    kernel.  Row 0 = W [K][Cin][Cout] (dgrad operand), row 1 = W^T [K][Cout][Cin] (forward operand); rebuilt when the parameter's
+    version counter moved"""
     import weakref
-    hit = _WQ.get(id(w)) if w.is_leaf else None
+    hit = _WQ.get((id(w), planes)) if w.is_leaf else None
     if hit is not None and hit[0]() is w and hit[1] == w._version:
         return hit[2]
-    q = torch.empty((2, w.numel()), dtype=torch.bfloat16, device=w.device)
-    check(lib().btc_weights_to_bf16(ptr(w), int(K), int(cin), int(cout), ptr(q[0]), ptr(q[1]), stream_ptr()), "btc_weights_to_bf16")
+    q = torch.empty((2, planes * w.numel()), dtype=torch.bfloat16, device=w.device)
+    name = "btc_weights_to_bf16" if planes == 1 else "btc_weights_split3"
+    check(getattr(lib(), name)(ptr(w), int(K), int(cin), int(cout), ptr(q[0]), ptr(q[1]), stream_ptr()), name)
     if not w.is_leaf:   # a temporary (the zero-padded 34 -> 48 channel weight is a fresh tensor every step): not cached
         return q
     for k in [k for k, v in _WQ.items() if v[0]() is None]:   # every miss drops the entries of freed parameters
         del _WQ[k]
-    _WQ[id(w)] = (weakref.ref(w), w._version, q)
+    _WQ[(id(w), planes)] = (weakref.ref(w), w._version, q)
     return q
 
 
-_WS3 = {}
-_SCRATCH = {}
-
-
-def _split_operands(src, K, cred, cres, n_rows):
-    """fp32 launch on the split-operand kernel (csrc/conv_apply_split.hip: three bf16 pieces per operand, six bf16 MFMAs per
-    product block)?  The library's policy (btc_conv_split_wanted; never under BTC_TUNE_SPLIT = 1) -- same as binding.cpp"""
-    if not (src.dtype == torch.float32 and lib().btc_conv_split_wanted(int(K), int(cred), int(cres), int(n_rows)) == 1):
-        return False
-    if src.numel() * 4 >= 0xFFFFFF00:    # the kernel's gathers use 32-bit byte offsets (it traps past them): the exact kernels take any size
-        return False
-    key = (src.device.index, stream_ptr())
-    if key not in _SCRATCH:    # the stream's scratch buffer for z-split launches (btc_set_scratch), as binding.cpp ensure_scratch
-        buf = _SCRATCH[key] = torch.empty(48 << 20, dtype=torch.uint8, device=src.device)
-        check(lib().btc_set_scratch(stream_ptr(), ptr(buf), buf.numel()), "btc_set_scratch")
-    return True
-
-
-def _weights_split(w, K, cin, cout):
-    """(2, 3 * numel) bf16: row 0 = the hi | mid | lo planes of W [K][Cin][Cout] (dgrad operand), row 1 = those of W^T (forward
-    operand); rebuilt when the parameter's version counter moved"""
-    import weakref
-    hit = _WS3.get(id(w)) if w.is_leaf else None
-    if hit is not None and hit[0]() is w and hit[1] == w._version:
-        return hit[2]
-    q = torch.empty((2, 3 * w.numel()), dtype=torch.bfloat16, device=w.device)
-    check(lib().btc_weights_split3(ptr(w), int(K), int(cin), int(cout), ptr(q[0]), ptr(q[1]), stream_ptr()), "btc_weights_split3")
-    if not w.is_leaf:
-        return q
-    for k in [k for k, v in _WS3.items() if v[0]() is None]:
-        del _WS3[k]
-    _WS3[id(w)] = (weakref.ref(w), w._version, q)
-    return q
+def _operands(src, w, K, cred, cres, n_rows, fwd):
+    """the operands of one apply launch -> (BTC_OPERANDS_* code, weight tensor for this pass); the policy of binding.cpp operands_of:
+    bf16 src : 2, a bf16 copy of the weights on the bf16 matrix pipe (csrc/conv_apply_bf16.hip) where the kernel takes the shape and
+               the tuning key BTC_TUNE_BF16_OPERANDS is not 1; else 1, fp32 weights
+    fp32 src : 3, the three bf16 planes on the split-operand kernel (csrc/conv_apply_split.hip) where the library wants it
+               (btc_conv_split_wanted; never under BTC_TUNE_SPLIT = 1) and its 32-bit byte offsets reach all of src (the C entry
+               refuses past 4 GB) -- the stream's scratch buffer is registered on the way; else 0, the exact fp32 kernels"""
+    L = lib()
+    K, cred, cres = int(K), int(cred), int(cres)
+    planes = 0
+    if src.dtype == torch.bfloat16:
+        if L.btc_conv_bf16w_supported(K, cred, cres) == 1 and L.btc_tune_value(8) != 1:
+            planes = 1
+    elif src.dtype == torch.float32 and L.btc_conv_split_wanted(K, cred, cres, int(n_rows)) == 1 and src.numel() * 4 < 0xFFFFFF00:
+        key = (src.device.index, stream_ptr())
+        if key not in _SCRATCH:
+            buf = _SCRATCH[key] = torch.empty(48 << 20, dtype=torch.uint8, device=src.device)
+            check(L.btc_set_scratch(stream_ptr(), ptr(buf), buf.numel()), "btc_set_scratch")
+        planes = 3
+    if not planes:
+        return (1 if src.dtype == torch.bfloat16 else 0), w
+    q = _weights_q(w, K, cred if fwd else cres, cres if fwd else cred, planes)
+    return (2 if planes == 1 else 3), q[1 if fwd else 0]
 
 
 def _conv_forward(features, w, b, map_fwd, ord_fwd=None):
@@ -609,21 +586,10 @@ def _conv_forward(features, w, b, map_fwd, ord_fwd=None):
         raise _lib.BtcHipError(f"weight {tuple(w.shape)} does not match K={K}, Cin={features.shape[1]}")
     n_res = map_fwd.shape[0]
     out = torch.empty((n_res, cout), dtype=features.dtype, device=features.device)
-    if _bf16_operands(features, K, cin, cout):
-        q = _weights_bf16(w, K, cin, cout)
-        with _span("conv_apply", _conv_cost, (map_fwd, n_res, K, cin, cout, 2)):
-            check(lib().btc_conv_apply_ordered(0, 2, ptr(features), ptr(q[1]), ptr(b), ptr(map_fwd), ptr(ord_fwd), n_res, K, cin, cout, ptr(out),
-                                               stream_ptr()), "btc_conv_apply_ordered")
-        return out
-    if _split_operands(features, K, cin, cout, n_res):
-        q = _weights_split(w, K, cin, cout)
-        with _span("conv_apply", _conv_cost, (map_fwd, n_res, K, cin, cout, 4)):
-            check(lib().btc_conv_apply_src(0, 3, ptr(features), int(features.shape[0]), ptr(q[1]), ptr(b), ptr(map_fwd), ptr(ord_fwd), n_res, K, cin, cout,
-                                           ptr(out), stream_ptr()), "btc_conv_apply_src")
-        return out
+    operands, wq = _operands(features, w, K, cin, cout, n_res, True)
     with _span("conv_apply", _conv_cost, (map_fwd, n_res, K, cin, cout, 2 if bf else 4)):
-        check(lib().btc_conv_apply_ordered(0, 1 if bf else 0, ptr(features), ptr(w), ptr(b), ptr(map_fwd), ptr(ord_fwd), n_res, K, cin, cout,
-                                           ptr(out), stream_ptr()), "btc_conv_apply_ordered")
+        check(lib().btc_conv_apply_src(0, operands, ptr(features), int(features.shape[0]), ptr(wq), ptr(b), ptr(map_fwd), ptr(ord_fwd), n_res, K, cin, cout,
+                                       ptr(out), stream_ptr()), "btc_conv_apply_src")
     return out
 
 
@@ -644,7 +610,7 @@ def _conv_backward(features, w, map_fwd, map_bwd, grad_out, wshape, need_din, ne
         F = fast()
         if F is not None:
             return F.conv_bwd(features, w, map_fwd, map_bwd, ord_bwd, grad_out, bool(need_din), bool(need_dw), overlap, bool(allow_defer), stream_ptr())
-    side = _side_stream(dev) if (overlap and PROFILE is None) else None
+    side = _own_stream("wgrad", dev) if (overlap and PROFILE is None) else None
     if need_dw:
         ws_bytes = L.btc_conv_wgrad_ws_bytes(n_res, K, cin, cout, n_src)
         if side is not None:
@@ -666,17 +632,9 @@ def _conv_backward(features, w, map_fwd, map_bwd, grad_out, wshape, need_din, ne
     if need_din:
         din = torch.empty((n_src, cin), dtype=features.dtype, device=dev)
         with _span("conv_apply", _conv_cost, (map_bwd, n_src, K, cout, cin, 2 if bf else 4)):
-            if _bf16_operands(grad_out, K, cout, cin):
-                q = _weights_bf16(w, K, cin, cout)
-                check(L.btc_conv_apply_ordered(pass_dgrad, 2, ptr(grad_out), ptr(q[0]), None, ptr(map_bwd), ptr(ord_bwd), n_src, K, cin, cout, ptr(din),
-                                               stream_ptr()), "btc_conv_apply_ordered")
-            elif _split_operands(grad_out, K, cout, cin, n_src):
-                q = _weights_split(w, K, cin, cout)
-                check(L.btc_conv_apply_src(pass_dgrad, 3, ptr(grad_out), int(grad_out.shape[0]), ptr(q[0]), None, ptr(map_bwd), ptr(ord_bwd), n_src, K, cin,
-                                           cout, ptr(din), stream_ptr()), "btc_conv_apply_src")
-            else:
-                check(L.btc_conv_apply_ordered(pass_dgrad, 1 if bf else 0, ptr(grad_out), ptr(w), None, ptr(map_bwd), ptr(ord_bwd), n_src, K, cin, cout,
-                                               ptr(din), stream_ptr()), "btc_conv_apply_ordered")
+            operands, wq = _operands(grad_out, w, K, cout, cin, n_src, False)
+            check(L.btc_conv_apply_src(pass_dgrad, operands, ptr(grad_out), int(grad_out.shape[0]), ptr(wq), None, ptr(map_bwd), ptr(ord_bwd), n_src, K, cin,
+                                       cout, ptr(din), stream_ptr()), "btc_conv_apply_src")
     if side is not None:
         torch.cuda.current_stream().wait_stream(side)  # join: dW is consumed on the main stream from here on
         dw.record_stream(torch.cuda.current_stream())

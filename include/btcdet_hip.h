@@ -266,7 +266,7 @@ int btc_conv_dgrad_bf16w(const void* dout, const void* w_bf16, const int32_t* nb
  * (tests/test_hip_split.py).  For the layers whose matrix phase is the long pole: Cred % 32 == 0, Cres % 32 == 0.
  *   btc_weights_split3 : W fp32 [K][Cin][Cout] -> w_split [3][K][Cin][Cout] bf16 (dgrad operand), wt_split [3][K][Cout][Cin]
  *                        (forward operand); once per optimizer step and layer (3*K*Cin*Cout*2 bytes each)
- * used through btc_conv_apply_ordered / btc_conv_bn_relu_fwd with operands = BTC_OPERANDS_F32_SPLIT and W = the planes of that pass */
+ * used through btc_conv_apply_src / btc_conv_bn_relu_fwd_src with operands = BTC_OPERANDS_F32_SPLIT and W = the planes of that pass */
 int btc_conv_split_supported(int K, int Cred, int Cres);
 /* Scratch memory for a stream: `bytes` of device memory the library may use during any launch on `stream` (the caller owns it and
  * keeps it alive until it registers another buffer, or NULL, for that stream).  Used by the split-operand kernel on levels of a few
