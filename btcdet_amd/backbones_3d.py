@@ -74,23 +74,6 @@ def _to_feature_dtype(x, dtype):
     return x
 
 
-def _strided(seq):
-    """first sparse layer of a SparseSequential stage if it builds its own (strided / transposed / dilating) rulebook"""
-    m = seq[0]
-    while isinstance(m, spconv.SparseSequential):
-        m = m[0]
-    return m if isinstance(m, spconv.SparseConvolution) and not m.subm and not m.inverse else None
-
-
-def _chain_lookahead(stages):
-    """stage i's rulebook-building layer announces stage i+1's: its row count starts on the side stream as soon as the level
-    it consumes exists (spconv/ops.py LOOKAHEAD).  Plain attribute, not a submodule registration."""
-    layers = [l for l in (_strided(s) for s in stages) if l is not None]
-    for a, b in zip(layers[:-1], layers[1:]):
-        a.__dict__['lookahead'] = (b,)
-    return layers[0] if layers else None
-
-
 def _seq(specs, norm_fn):
     """specs: list of (cin, cout, k, dict(kwargs)) -> SparseSequential of post_act_blocks"""
     return spconv.SparseSequential(*[post_act_block(ci, co, k, norm_fn=norm_fn, **kw) for ci, co, k, kw in specs])
@@ -119,7 +102,6 @@ class VoxelBackBoneDeconv(nn.Module):
         self.deconv5 = _seq([(c[1], c[1], 3, dict(stride=2, padding=1, indice_key='spconv5', conv_type='spdeconv')),
                              (c[1], c[1], 3, dict(padding=1, indice_key='subm5'))], norm_fn)
         self.num_point_features = c[1]
-        _chain_lookahead([self.conv1, self.conv2, self.conv3, self.deconv4, self.deconv5])
 
     def forward(self, batch_dict):
         voxel_features, voxel_coords = batch_dict['voxel_features'], batch_dict['voxel_coords'].int()
@@ -164,15 +146,15 @@ class VoxelBackBoneDeconv(nn.Module):
         merged_head = head is not None and hasattr(head, "_merge_ok") and head._merge_ok()
         if sp_ops.fast() is not None and (head is None or merged_head or hasattr(head, "conv_cls")):
             # one call of the compiled binding for all rulebooks (spconv/geometry.py); the plan is fixed per (model, batch size)
-            from .spconv.geometry import GeometryPlan, flatten_convs
-            plans = self.__dict__.setdefault("_geometry_plans", {})
-            key = (int(bs), id(head))
-            plan = plans.get(key)
-            if plan is None:
-                convs = flatten_convs(*stages)
+            from .spconv.geometry import cached_plan
+            def plan_stages():
+                out = list(stages)
                 if head is not None:
-                    convs += flatten_convs(head.conv_cls) + (flatten_convs(head.conv_res) if getattr(head, "reg", False) else [])
-                plan = plans[key] = GeometryPlan(convs, self.sparse_shape, bs)
+                    out.append(head.conv_cls)
+                    if getattr(head, "reg", False):
+                        out.append(head.conv_res)
+                return out
+            plan = cached_plan(self, (int(bs), id(head)), plan_stages, self.sparse_shape, bs)
             indice_dict = {}
             plan.run(voxel_coords, indice_dict)
             batch_dict['occ_geometry'] = (voxel_coords, indice_dict)
@@ -207,7 +189,7 @@ class VoxelBackBoneDeconv(nn.Module):
         return x
 
 
-DET_GEOMETRY_WALK = True  # VoxelBackBone8xOcc._walk_geometry (False: the layers build their rulebooks one by one; tests flip it)
+DET_GEOMETRY_WALK = True  # VoxelBackBone8xOcc._walk_geometry (False: every layer builds its own rulebook; tests/test_hip_det_backbone.py flips it)
 FAST_STAGES = True        # VoxelBackBone8xOcc._stage: stages straight into the compiled chain call
 
 
@@ -260,10 +242,6 @@ class VoxelBackBone8xOcc(nn.Module):
                 setattr(self, 'squeeze_z_conv%d' % (i + 1), spconv.SparseSequential(post_act_block(
                     ch, ch // 2, 3, norm_fn=norm_fn, padding=1, indice_key='submsqueez%d' % (i + 1), conv_type='subm2d')))
         self._build_combine_net(norm_fn, c, self.out_feat_type[4])
-        stages = [self.conv2, self.conv3, self.conv4, self.conv_out]
-        if getattr(self, "squeezeBev", None) is not None:
-            stages.append(self.squeezeBev)
-        self.__dict__['_first_strided'] = _chain_lookahead(stages)
         # the strided levels of the rulebook walk built beside the first stage on a side stream (True), or the whole walk first with one
         # blocking read-back (False).  Per instance: a schedule that already runs the branch on a stream of its own switches it off
         # (HotPathTrainer, pipelined: a fifth active stream costs 1.8 ms per step there).
@@ -274,29 +252,12 @@ class VoxelBackBone8xOcc(nn.Module):
         binding before the first layer runs (spconv/geometry.py): every stage then finds its rulebooks ready and runs as one
         compiled call (SparseSequential._chain_plan) instead of ~100 us of Python per layer; the side-branch pools and the
         down2 / down3 / down_combine layers reuse these rulebooks through the geometry cache / their indice_keys as before.
-        False when the compiled binding is not in use (the layers then build their rulebooks one by one, with lookahead)."""
+        False when the compiled binding is not in use (every layer then builds its own rulebook, synchronously)."""
         from .spconv import ops as sp_ops
         if not (DET_GEOMETRY_WALK and coords.is_cuda and sp_ops.fast() is not None and sp_ops.CAPTURE is None):
             return False
-        from .spconv.geometry import GeometryPlan, flatten_convs
-        plans = self.__dict__.setdefault("_geometry_plans", {})
-        plan = plans.get(int(bs))
-        if plan is None:
-            # every sparse conv of forward() in execution order: the main chain builds, the side layers (conv1_combine, down2, down3,
-            # down_combine) reuse by indice_key -- the plan then hands forward() one rulebook per layer (stage_rulebooks)
-            stages = [self.conv1, self.conv1_combine, self.conv2, self.conv2_combine, self.conv3, self.conv3_combine, self.conv4, self.conv4_combine,
-                      self.conv_out]
-            if getattr(self, "squeezeBev", None) is not None:
-                stages.append(self.squeezeBev)
-            if getattr(self, "down3", None) is not None:
-                stages += [self.down2, self.down3, self.down_combine]
-            plan = plans[int(bs)] = GeometryPlan(flatten_convs(*stages), self.sparse_shape, bs)
-            offs, pos = {}, 0
-            for st in stages:
-                n = len(flatten_convs(st))
-                offs[id(st)] = (pos, pos + n)
-                pos += n
-            plan.stage_slices = offs
+        from .spconv.geometry import cached_plan
+        plan = cached_plan(self, int(bs), self._plan_stages, self.sparse_shape, bs)
         if allow_async and self.walk_async and sp_ops.PROFILE is None and plan.entries[0][0] == 0:
             # The first stage (conv1, conv1_combine) only needs the level-0 submanifold rulebook, which needs no read-back: build it
             # alone, fork the rest of the walk (the strided levels and the read-back of their row counts) onto a side stream, and
@@ -310,6 +271,17 @@ class VoxelBackBone8xOcc(nn.Module):
             return (plan, plan.start(coords, side_stream=True), {0: rb0}, coords)
         return ("done", plan, plan.run(coords, indice_dict))
 
+    def _plan_stages(self):
+        """every sparse conv of forward() in execution order: the main chain builds, the side layers (conv1_combine, down2, down3,
+        down_combine) reuse by indice_key -- the plan then hands forward() one rulebook per layer (_stage)"""
+        stages = [self.conv1, self.conv1_combine, self.conv2, self.conv2_combine, self.conv3, self.conv3_combine, self.conv4, self.conv4_combine,
+                  self.conv_out]
+        if getattr(self, "squeezeBev", None) is not None:
+            stages.append(self.squeezeBev)
+        if getattr(self, "down3", None) is not None:
+            stages += [self.down2, self.down3, self.down_combine]
+        return stages
+
     @staticmethod
     def _finish_walk(walk, indice_dict):
         """-> (plan, one rulebook per sparse conv of the plan) once the walk is complete, else None"""
@@ -321,26 +293,14 @@ class VoxelBackBone8xOcc(nn.Module):
         return None
 
     def _stage(self, stage, x, ready):
-        """run a SparseSequential stage.  With the walk's rulebooks at hand (ready = (plan, rulebooks)) a pure conv -> BatchNorm -> ReLU
-        stage goes straight into ONE call of the compiled binding (SparseSequential._run_chain) -- no module call, no rulebook
-        look-ups, no per-layer Python: the training thread's forward pass is bound by exactly that"""
-        from .spconv import fused_bn as sp_fused_bn, modules as sp_modules, ops as sp_ops
-        if ready is not None and sp_modules.CHAIN_LAYERS and sp_modules.FUSE_CONV_BN and sp_modules.FUSE_BN_RELU and sp_ops.PROFILE is None \
-                and sp_ops.CAPTURE is None and sp_ops.NATIVE_AUTOGRAD and sp_ops.fast() is not None:   # (the conditions of SparseSequential's own chain path)
-            plan, rbs = ready
-            sl = plan.stage_slices.get(id(stage))
-            triples = stage.__dict__.get("_chain_triples", False)
-            if triples is False:
-                stage._chain_plan(x)                      # derives and caches the stage's (conv, bn, relu) triples
-                triples = stage.__dict__.get("_chain_triples", None)
-            f = x.features
-            if sl is not None and triples and len(triples) == sl[1] - sl[0] and f.is_cuda and f.shape[0] > 0 and \
-                    all(sp_fused_bn.fusable(bn) for _, bn, _ in triples) and \
-                    (f.dtype == torch.float32 or all(c.in_channels % 16 == 0 and c.out_channels % 16 == 0 for c, _, _ in triples)):
-                mine = rbs[sl[0]:sl[1]]
-                if all(rb is not None and rb.n_out > 0 for rb in mine):
-                    steps = [(c, bn, relu, rb, False) for (c, bn, relu), rb in zip(triples, mine)]
-                    return stage._run_chain(x, steps, mine[-1].out_indices, plan.entries[sl[1] - 1][4])
+        """run a SparseSequential stage.  With the walk's rulebooks at hand (ready = (plan, rulebooks)) the stage's slice of them goes
+        to the gate of the compiled chain call (SparseSequential._chain_plan) and from there into ONE call of the binding -- no module
+        call, no rulebook look-ups, no per-layer Python: the training thread's forward pass is bound by exactly that"""
+        sl = ready[0].stage_slices.get(id(stage)) if ready is not None else None
+        if sl is not None:
+            chain = stage._chain_plan(x, ready[1][sl[0]:sl[1]])
+            if chain is not None:
+                return stage._run_chain(x, *chain)
         return stage(x)
 
     def _stages(self, stages, x, ready):
@@ -464,9 +424,6 @@ class VoxelBackBone8xOcc(nn.Module):
             walk = pre[2]
         else:
             walk = self._walk_geometry(coords, bs, x.indice_dict)
-        if not walk and self._first_strided is not None:
-            # conv2's row count runs beside conv1 (rulebook lookahead, spconv/ops.py)
-            self._first_strided.prefetch(coords, self.sparse_shape, bs, x.indice_dict)
         n_occ = len(self.occ_conv_exec)
         ready = None
         if FAST_STAGES and isinstance(walk, tuple) and walk[0] == "done":   # the blocking walk: every rulebook is there already

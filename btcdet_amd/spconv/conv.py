@@ -91,7 +91,7 @@ class SparseConvolution(SparseModule):
 
     def _resolve_rulebook(self, input, out_spatial_shape):
         """the geometry half of forward: this layer's rulebook (cached under indice_key / the geometry cache, or built now), the
-        output index tensor and spatial shape; announces the next strided layers (lookahead)"""
+        output index tensor and spatial shape"""
         indices, spatial_shape, batch_size = input.indices, input.spatial_shape, input.batch_size
         rb = input.find_indice_pair(self.indice_key)
         if self.inverse:
@@ -106,10 +106,6 @@ class SparseConvolution(SparseModule):
         outids = rb.out_indices
         if self.ndim == 2 and outids.shape[1] == 4:
             outids = torch.cat([outids[:, :1], outids[:, 2:]], dim=1).contiguous()
-        # the strided layers that consume this output level start counting their rows now, on the side stream,
-        # while this layer's (and the following submanifold layers') feature kernels run (ops.py, LOOKAHEAD)
-        for nxt in getattr(self, "lookahead", ()):
-            nxt.prefetch(outids, out_spatial_shape, batch_size, input.indice_dict)
         return rb, outids, out_spatial_shape
 
     def forward_geometry(self, input):
@@ -148,7 +144,9 @@ class SparseConvolution(SparseModule):
     # A rulebook is a pure function of (indices, geometry): layers that ask for the same geometry on the same index
     # tensor under different indice_keys (OccHead3D's 'cls_ind' / 'res_ind' after 'subm5', occ_head_3D.py:26,31; a
     # SparseMaxPool3d beside a SparseConv3d, spconv_backbone.py:831-847) share one build.  The cache lives in the shared
-    # indice_dict and keeps the index tensor alive, so a recycled data_ptr can never alias.
+    # indice_dict, every value is (Rulebook, index tensor), and it keeps the index tensor alive, so a recycled data_ptr can never
+    # alias.  A layer that finds no rulebook builds one synchronously; whoever wants them ahead of time builds them all at once
+    # (spconv/geometry.py).
     def _gkey(self, indices, spatial_shape):
         return geometry_key(indices, spatial_shape, self.kernel_size, self.dilation, self.subm, self.transposed, self.stride,
                             self.padding, self.output_padding)
@@ -158,11 +156,7 @@ class SparseConvolution(SparseModule):
         gkey = self._gkey(indices, spatial_shape)
         hit = geom.get(gkey, None)
         if hit is not None:
-            rb = hit[0]
-            if isinstance(rb, ops.PendingRulebook):
-                rb = rb.finish()
-                geom[gkey] = (rb, indices)
-            return rb
+            return hit[0]
         idx4 = indices
         if self.ndim == 2:
             idx4 = torch.cat([indices[:, :1], torch.zeros_like(indices[:, :1]), indices[:, 1:]], dim=1)
@@ -180,19 +174,6 @@ class SparseConvolution(SparseModule):
                                           self._k3(self.padding, 0), self._k3(self.dilation, 1), self._k3(self.output_padding, 0), self.subm,
                                           self.transposed)
         return g
-
-    def prefetch(self, indices, spatial_shape, batch_size, indice_dict):
-        """start the count half of this layer's rulebook for `indices` (no-op for submanifold / inverse / 2-D / cached layers)"""
-        if self.subm or self.inverse or self.conv1x1 or self.ndim != 3 or not indices.is_cuda:
-            return
-        if not ops.lookahead_enabled() or (self.indice_key is not None and self.indice_key in indice_dict):
-            return
-        geom = indice_dict.setdefault("__geometry_cache__", {})
-        gkey = self._gkey(indices, spatial_shape)
-        if gkey in geom:
-            return
-        geom[gkey] = (ops.prefetch_conv_rulebook(indices, batch_size, spatial_shape, self.kernel_size, self.stride, self.padding,
-                                                 self.dilation, self.output_padding, self.transposed), indices)
 
     def _k3(self, v, fill):
         return list(v) if self.ndim == 3 else [fill] + list(v)

@@ -1,5 +1,6 @@
 """Rulebooks of a whole chain of sparse layers from the input coordinates alone, in ONE call of the compiled binding
-(binding.cpp geometry_walk) -- what SparseConvolution.forward_geometry does layer by layer in Python.  The plan (which layer
+(binding.cpp geometry_walk) -- what SparseConvolution.forward_geometry does layer by layer in Python.  This is THE way to have
+rulebooks before they are needed: a layer that finds none builds its own synchronously (ops._build_rulebook).  The plan (which layer
 builds, which reuses an earlier layer's rulebook through its indice_key or through an identical geometry on the same level,
 which inverse layer returns to which level) is derived once per (layer list, input shape); running it fills the
 indice_dict / geometry cache exactly as the layer-by-layer walk would, so a later forward finds every rulebook ready."""
@@ -27,6 +28,22 @@ def _sig(conv):
         return (k, d, True, False)
     return (k, d, False, bool(conv.transposed), tuple(int(v) for v in conv.stride), tuple(int(v) for v in conv.padding),
             tuple(int(v) for v in conv.output_padding))
+
+
+def cached_plan(owner, key, stages, spatial_shape, batch_size):
+    """the GeometryPlan over the sparse convs of stages() -- a callable, evaluated on a miss only -- built once per (owner, key) and kept on
+    the owner; plan.stage_slices[id(stage)] = (first, last + 1) are the stage's layers in the plan (and in the lists run() / finish() return)"""
+    plans = owner.__dict__.setdefault("_geometry_plans", {})
+    plan = plans.get(key)
+    if plan is None:
+        convs, slices = [], {}
+        for st in stages():
+            mine = flatten_convs(st)
+            slices[id(st)] = (len(convs), len(convs) + len(mine))
+            convs += mine
+        plan = plans[key] = GeometryPlan(convs, spatial_shape, batch_size)
+        plan.stage_slices = slices
+    return plan
 
 
 class GeometryPlan(object):

@@ -87,26 +87,19 @@ class SparseSequential(SparseModule):
                 out.append(m)
         return out
 
-    def _chain_plan(self, input):
-        """[(conv, bn, relu, rulebook, inverse)] when this container is nothing but conv -> BatchNorm1d (-> ReLU) layers whose
-        rulebooks ALL exist already in input.indice_dict (by indice_key or in the geometry cache -- the occupancy branch after
-        BtcHotPath.prepare), else None.  No rulebook is built and no dict is written here."""
-        from . import fused_bn, ops
-        from .conv import SparseConvolution
-        f = input.features
-        if not (FUSE_CONV_BN and FUSE_BN_RELU and CHAIN_LAYERS and f is not None and f.is_cuda and f.shape[0] > 0
-                and f.dtype in (nn_float32, _torch.bfloat16)):
-            return None
-        # the container's structure is fixed: its (conv, bn, relu) triples are derived once (None: not a pure conv -> BatchNorm -> ReLU chain)
+    def _triples(self):
+        """the container's (conv, bn, relu) triples, derived once: its structure is fixed (None: not a pure conv -> BatchNorm -> ReLU chain)"""
         triples = self.__dict__.get("_chain_triples", False)
         if triples is False:
+            from . import ops
+            from .conv import SparseConvolution
             mods = self._flat_modules()
             triples, i = [], 0
             while i < len(mods):
                 conv = mods[i]
                 bn = mods[i + 1] if i + 1 < len(mods) else None
                 # structure only (a BatchNorm1d behind a 3-D sparse conv): whether the BatchNorm is fusable IN ITS CURRENT STATE is asked per
-                # call below -- an eval sanity pass before training must not switch the fast path off for good
+                # call in _chain_plan -- an eval sanity pass before training must not switch the fast path off for good
                 if not (isinstance(conv, SparseConvolution) and not conv.conv1x1 and conv.ndim == 3 and isinstance(bn, nn.BatchNorm1d)) \
                         or ops.pads_in_channels(conv.in_channels):   # (padded per layer: ops._pad_in_channels)
                     triples = None
@@ -115,30 +108,46 @@ class SparseSequential(SparseModule):
                 triples.append((conv, bn, relu))
                 i += 2 + int(relu)
             self.__dict__["_chain_triples"] = triples
-        if not triples:
+        return triples
+
+    def _chain_plan(self, input, rulebooks=None):
+        """THE gate of the compiled chain call: ([(conv, bn, relu, rulebook, inverse)], output indices, output shape) when the
+        switches allow it, this container is nothing but conv -> BatchNorm1d (-> ReLU) layers and their rulebooks ALL exist and
+        are non-empty, else None.  rulebooks: one per sparse layer, handed over by a caller that has them in a list
+        (VoxelBackBone8xOcc._stage after the geometry walk) -- then no dict is read; None: they are looked up in
+        input.indice_dict, by indice_key or in the geometry cache (the occupancy branch after BtcHotPath.prepare).  No rulebook
+        is built and no dict is written here."""
+        from . import fused_bn, ops
+        f = input.features
+        if not (FUSE_CONV_BN and FUSE_BN_RELU and CHAIN_LAYERS and ops.PROFILE is None and ops.CAPTURE is None and ops.NATIVE_AUTOGRAD
+                and f is not None and f.is_cuda and f.shape[0] > 0 and f.dtype in (nn_float32, _torch.bfloat16) and ops.fast() is not None):
+            return None
+        triples = self._triples()
+        if not triples or (rulebooks is not None and len(rulebooks) != len(triples)):
             return None
         plan = []
         indices, shape = input.indices, input.spatial_shape
-        geom = input.indice_dict.get("__geometry_cache__", None)
-        for conv, bn, relu in triples:
+        geom = input.indice_dict.get("__geometry_cache__", None) if rulebooks is None else None
+        for i, (conv, bn, relu) in enumerate(triples):
             if not fused_bn.fusable(bn):    # (a BatchNorm switched to eval without running statistics, ...)
                 return None
             if f.dtype == _torch.bfloat16 and (conv.in_channels % 16 or conv.out_channels % 16):
                 return None
-            rb = input.indice_dict.get(conv.indice_key, None) if conv.indice_key is not None else None
+            if rulebooks is not None:
+                rb = rulebooks[i]
+            else:
+                rb = input.indice_dict.get(conv.indice_key, None) if conv.indice_key is not None else None
+                if rb is None and not conv.inverse and geom is not None:
+                    hit = geom.get(conv._gkey(indices, shape), None)
+                    rb = hit[0] if hit is not None else None
+            if rb is None or (rb.n_in if conv.inverse else rb.n_out) == 0:
+                return None
             if conv.inverse:
-                if rb is None or rb.n_in == 0:
-                    return None
                 indices, shape = rb.in_indices, rb.in_shape[3 - conv.ndim:]
             else:
-                if rb is None:
-                    hit = geom.get(conv._gkey(indices, shape), None) if geom is not None else None
-                    rb = hit[0] if hit is not None else None
-                if rb is None or isinstance(rb, ops.PendingRulebook) or rb.n_out == 0:
-                    return None
-                indices, shape = rb.out_indices, conv._out_shape(shape)
+                indices, shape = rb.out_indices, rb.out_shape
             plan.append((conv, bn, relu, rb, conv.inverse))
-        return (plan, indices, shape) if plan else None
+        return plan, indices, shape
 
     def _run_chain(self, input, plan, indices, shape):
         from . import fused_bn, ops
@@ -178,9 +187,9 @@ class SparseSequential(SparseModule):
         return out_tensor
 
     def forward(self, input):
-        from . import fused_bn, ops
+        from . import fused_bn
         from .conv import SparseConvolution
-        if isinstance(input, SparseConvTensor) and ops.PROFILE is None and ops.CAPTURE is None and ops.NATIVE_AUTOGRAD and ops.fast() is not None:
+        if isinstance(input, SparseConvTensor):
             plan = self._chain_plan(input)
             if plan is not None:
                 return self._run_chain(input, *plan)

@@ -7,7 +7,6 @@ spconv_backbone.py:12-29).  The rulebook is kept as two dense neighbour maps (se
 include/btcdet_hip.h); ``Rulebook.indice_pairs()`` gives spconv's (2,K,N)/(K,) view on demand.
 """
 import os
-import threading
 
 import numpy as np
 import torch
@@ -69,9 +68,9 @@ OVERLAP_WGRAD = True  # run wgrad on a side stream concurrently with dgrad (back
 _STREAMS = {}
 
 
-def _own_stream(kind, device):
-    """this module's stream of one kind per device: "wgrad" (beside dgrad) or "rulebook" (the count half of a strided rulebook)"""
-    key = (kind, device.index if device.index is not None else torch.cuda.current_device())
+def _wgrad_stream(device):
+    """this module's side stream per device: wgrad beside dgrad"""
+    key = device.index if device.index is not None else torch.cuda.current_device()
     st = _STREAMS.get(key)
     if st is None:
         st = _STREAMS[key] = torch.cuda.Stream(device=device)
@@ -309,16 +308,30 @@ def _build_rulebook(indices, batch_size, g):
         check(L.btc_rulebook_subm(ptr(indices), n, int(batch_size), g.p_in, g.p_k, g.p_d, ptr(nbr_out), None, ptr(ws), ws_bytes,
                                   stream_ptr()), "btc_rulebook_subm")
         return Rulebook(indices, indices, nbr_out, None, g.in_list, g.out_list, K, g.mode)
-    if PROFILE is not None:
-        return _start_conv_rulebook(indices, batch_size, g, None).finish()
-    # synchronous build: count, one blocking 4-byte read-back (spconv syncs at the same point), fill
+    # synchronous build: count, one blocking 4-byte read-back (spconv syncs at the same point), fill.  While profiling the two
+    # calls are two "rulebook" records (half = "count" / "fill") with the read-back between the spans, inside neither
     ws_bytes = _conv_ws_bytes(g, batch_size)
     ws = workspace(ws_bytes, dev)
     d_n_out = torch.empty((1,), dtype=torch.int32, device=dev)
-    st = stream_ptr()
+    prof = PROFILE
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if prof is not None else None
+    if ev:
+        ev[0].record()
     check(L.btc_rulebook_conv_count(ptr(indices), n, int(batch_size), g.p_in, g.p_out, g.p_k, g.p_s, g.p_p, g.p_d, g.mode, ptr(d_n_out),
-                                    ptr(ws), ws_bytes, st), "btc_rulebook_conv_count")
-    return _fill_conv_rulebook(indices, batch_size, g, int(d_n_out.item()), ws, ws_bytes)
+                                    ptr(ws), ws_bytes, stream_ptr()), "btc_rulebook_conv_count")
+    if ev:
+        ev[1].record()
+    n_out = int(d_n_out.item())
+    if ev:
+        ev[2].record()
+    rb = _fill_conv_rulebook(indices, batch_size, g, n_out, ws, ws_bytes)
+    if ev:
+        ev[3].record()
+        # SURVEY.md §8d, rulebook: 16 N_in + 16 N_out + 8 sum_k P_k bytes (attributed to the fill half; the count half adds time only)
+        info = dict(rows=rb.n_out, n_in=rb.n_in, K=rb.K, pairs=_num_pairs(rb.nbr_out), mode=rb.mode, out_shape=list(rb.out_shape))
+        prof.records.append(("rulebook", ev[0], ev[1], 0, 0, dict(info, half="count")))
+        prof.records.append(("rulebook", ev[2], ev[3], 16 * rb.n_in + 16 * rb.n_out + 8 * _num_pairs(rb.nbr_out), 0, dict(info, half="fill")))
+    return rb
 
 
 def _conv_ws_bytes(g, batch_size):
@@ -336,122 +349,6 @@ def _fill_conv_rulebook(indices, batch_size, g, n_out, ws, ws_bytes):
     check(lib().btc_rulebook_conv_fill(ptr(indices), n, int(batch_size), g.p_in, g.p_out, g.p_k, g.p_s, g.p_p, g.p_d, g.mode, n_out,
                                        ptr(out_indices), ptr(nbr_out), ptr(nbr_in), ptr(ws), ws_bytes, stream_ptr()), "btc_rulebook_conv_fill")
     return _with_orders(Rulebook(out_indices, indices, nbr_out, nbr_in, g.in_list, g.out_list, K, g.mode))
-
-
-# ---- strided / transposed rulebooks in two halves -------------------------------------------------------------------
-# The number of output rows of such a rulebook is data dependent, and every tensor downstream is sized by it: the host
-# must read it back (spconv syncs at the same point).  A blocking read-back drains the stream -- and after each one the
-# host has to refill the queue kernel by kernel while the GPU runs dry (13 read-backs per step made ~2 of 10.6 ms idle).
-# So the COUNT half (mark reachable cells, rank them, n_out -> pinned host memory) runs on a side stream as soon as the
-# input indices exist -- a layer's `lookahead` list names the strided layers that consume its output level
-# (spconv/conv.py) -- and the FILL half runs in the consumer's forward: by then the count is long finished, the host
-# waits on its event only (not on the main stream) and keeps running ahead of the GPU.
-# Measured at KITTI size: with the halves managed in Python (ctypes route) neutral to negative -- stream contexts, events
-# and the pinned copy cost the host what the wait saved; managed inside the compiled binding (_btcfast.rulebook_conv_start /
-# _finish) +1.5 % (221 -> 224.5 scenes/s) -- see lookahead_enabled().
-def lookahead_enabled():
-    """on when the compiled binding manages the two halves (events, pinned slot and side stream in C++: 221 -> 224.5 scenes/s), off on
-    the ctypes route (its Python per event costs what the wait saved)"""
-    return fast() is not None
-
-
-_PIN = {}
-_PIN_LOCK = threading.Lock()
-
-
-def _pinned_slot():
-    """one int32 of pinned host memory from a small ring (a slot is reused 256 read-backs later); prepare() may run on a worker
-    thread beside the training thread, so slots are handed out under a lock"""
-    with _PIN_LOCK:
-        ring = _PIN.get("ring")
-        if ring is None:
-            ring = _PIN["ring"] = torch.zeros((256,), dtype=torch.int32).pin_memory()
-            _PIN["next"] = 0
-        i = _PIN["next"]
-        _PIN["next"] = (i + 1) % 256
-    return ring[i:i + 1]
-
-
-class PendingRulebook(object):
-    """count half issued, fill half outstanding"""
-
-    def __init__(self, indices, batch_size, g, ws, ws_bytes, host_n, event, prof_ev):
-        self.indices, self.batch_size, self.g = indices, batch_size, g
-        self.ws, self.ws_bytes, self.host_n, self.event, self.prof_ev = ws, ws_bytes, host_n, event, prof_ev
-
-    def finish(self):
-        self.event.synchronize()                        # host: the count (on the side stream) is done; the main stream is not drained
-        n_out = int(self.host_n[0])
-        main = torch.cuda.current_stream()
-        main.wait_event(self.event)                     # device: the fill below reads the bitmap / ranks the count wrote
-        self.ws.record_stream(main)
-        prof = PROFILE
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rb = _fill_conv_rulebook(self.indices, self.batch_size, self.g, n_out, self.ws, self.ws_bytes)
-        if prof is not None:
-            e1.record()
-            c0, c1 = self.prof_ev
-            # SURVEY.md §8d, rulebook: 16 N_in + 16 N_out + 8 sum_k P_k bytes (attributed to the fill half; the count half adds time only)
-            info = dict(rows=rb.n_out, n_in=rb.n_in, K=rb.K, pairs=_num_pairs(rb.nbr_out), mode=rb.mode, out_shape=list(rb.out_shape))
-            prof.records.append(("rulebook", c0, c1, 0, 0, dict(info, half="count")))
-            prof.records.append(("rulebook", e0, e1, 16 * rb.n_in + 16 * rb.n_out + 8 * _num_pairs(rb.nbr_out), 0, dict(info, half="fill")))
-        self.ws = None
-        return rb
-
-
-def _start_conv_rulebook(indices, batch_size, g, side):
-    """issue the count half on `side` (a torch stream) or, side=None, on the current stream"""
-    dev, n, L = indices.device, indices.shape[0], lib()
-    ws_bytes = _conv_ws_bytes(g, batch_size)
-    if side is not None:
-        side.wait_stream(torch.cuda.current_stream())   # the indices are produced on the main stream
-    ctx = torch.cuda.stream(side) if side is not None else _NOSPAN
-    prof_ev = None
-    with ctx:
-        if PROFILE is not None:
-            prof_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            prof_ev[0].record()
-        ws = workspace(ws_bytes, dev)
-        d_n_out = torch.empty((1,), dtype=torch.int32, device=dev)
-        check(L.btc_rulebook_conv_count(ptr(indices), n, int(batch_size), g.p_in, g.p_out, g.p_k, g.p_s, g.p_p, g.p_d, g.mode, ptr(d_n_out),
-                                        ptr(ws), ws_bytes, stream_ptr()), "btc_rulebook_conv_count")
-        if prof_ev is not None:
-            prof_ev[1].record()
-        host_n = _pinned_slot()
-        host_n.copy_(d_n_out, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-    if side is not None:
-        indices.record_stream(side)
-    return PendingRulebook(indices, batch_size, g, ws, ws_bytes, host_n, event, prof_ev)
-
-
-class _NativePending(PendingRulebook):
-    """the same two halves managed inside the compiled binding (events, pinned read-back slot and side stream in C++)"""
-
-    def __init__(self, F, handle, indices, g):
-        self.F, self.handle, self.indices, self.g = F, handle, indices, g
-
-    def finish(self):
-        g = self.g
-        out_indices, nbr_out, nbr_in, o_out, o_in = self.F.rulebook_conv_finish(self.handle)
-        self.handle = None
-        if not ROW_ORDER:
-            o_out = o_in = None
-        return Rulebook(out_indices, self.indices, nbr_out, nbr_in, g.in_list, g.out_list, g.K, g.mode, o_out, o_in)
-
-
-def prefetch_conv_rulebook(indices, batch_size, spatial_shape, ksize, stride=1, padding=0, dilation=1, out_padding=0, transpose=False):
-    """count half of a strided / transposed rulebook on the side stream; .finish() on the result gives the Rulebook"""
-    indices = _as_idx(indices)
-    g = _geometry(spatial_shape, ksize, stride, padding, dilation, out_padding, False, transpose)
-    F = fast() if PROFILE is None else None
-    if F is not None:
-        h = F.rulebook_conv_start(indices, int(batch_size), g.a_in, g.a_out, g.a_k, g.a_s, g.a_p, g.a_d, g.mode, g.K, _conv_ws_bytes(g, batch_size))
-        return _NativePending(F, h, indices, g)
-    return _start_conv_rulebook(indices, batch_size, g, _own_stream("rulebook", indices.device))
 
 
 def get_indice_pairs(indices, batch_size, spatial_shape, ksize=3, stride=1, padding=0, dilation=1, out_padding=0,
@@ -610,7 +507,7 @@ def _conv_backward(features, w, map_fwd, map_bwd, grad_out, wshape, need_din, ne
         F = fast()
         if F is not None:
             return F.conv_bwd(features, w, map_fwd, map_bwd, ord_bwd, grad_out, bool(need_din), bool(need_dw), overlap, bool(allow_defer), stream_ptr())
-    side = _own_stream("wgrad", dev) if (overlap and PROFILE is None) else None
+    side = _wgrad_stream(dev) if (overlap and PROFILE is None) else None
     if need_dw:
         ws_bytes = L.btc_conv_wgrad_ws_bytes(n_res, K, cin, cout, n_src)
         if side is not None:

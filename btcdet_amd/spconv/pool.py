@@ -31,16 +31,13 @@ class SparseMaxPool(SparseModule):
             out_spatial_shape = spatial_shape
         indices = input.indices
         # same geometry cache as the convolutions (conv.py): a pool beside a SparseConv3d with the same kernel / stride /
-        # padding on the same index tensor shares its rulebook (and a prefetched count half is finished here)
+        # padding on the same index tensor shares its rulebook
         geom = input.indice_dict.setdefault("__geometry_cache__", {})
         gkey = geometry_key(indices, spatial_shape, self.kernel_size, self.dilation, self.subm, False, self.stride, self.padding,
                             [0] * self.ndim)
         hit = geom.get(gkey, None)
         if hit is not None:
             rb = hit[0]
-            if isinstance(rb, ops.PendingRulebook):
-                rb = rb.finish()
-                geom[gkey] = (rb, indices)
         else:
             idx4, shape3 = indices, spatial_shape
             if self.ndim == 2:

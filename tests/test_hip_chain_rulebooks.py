@@ -96,6 +96,34 @@ def test_encoder_runs(chain, shape, n, B, mark_mode):
     _check_chain(_random_indices(rng, n, B, shape), B, shape, chain)
 
 
+@pytest.mark.parametrize("chain,shape,n,B", [(CHAIN, (9, 40, 60), 9000, 2)] + [(c, (27, 6, 5), 120, 1) for c in ENCODERS],
+                         ids=["chain"] + ["encoder%d" % i for i in range(len(ENCODERS))])
+def test_plan_and_layer_by_layer_build_the_same_rulebooks(chain, shape, n, B):
+    """the two ways a rulebook comes to be -- GeometryPlan.run (all of a chain in one call, one read-back) and a layer that finds none
+    and builds its own synchronously (forward_geometry, layer by layer) -- give the same levels and maps, layer for layer.  (The
+    row-order hints are not compared: the chain keys them differently and any permutation is valid, test_hip_row_order.py.)"""
+    from btcdet_amd import spconv
+    from btcdet_amd.spconv import ops
+    from btcdet_amd.spconv.geometry import GeometryPlan, flatten_convs
+    rng = np.random.default_rng(n + len(chain))
+    idx = torch.from_numpy(_random_indices(rng, n, B, shape)).to(DEV)
+    net = _net(chain)
+    planned = GeometryPlan(flatten_convs(net), shape, B).run(idx, {})
+    x = spconv.SparseConvTensor(None, idx, list(shape), B)
+    net.forward_geometry(x)
+    assert len(planned) == len(chain)
+    for (k, s, p, mode, key), a in zip(chain, planned):
+        b = x.indice_dict[key]
+        assert list(a.out_shape) == list(b.out_shape), key
+        assert torch.equal(a.out_indices, b.out_indices), key
+        assert torch.equal(a.nbr_out, b.nbr_out), key + " nbr_out"
+        assert torch.equal(a.nbr_in, b.nbr_in), key + " nbr_in"
+    cache = x.indice_dict["__geometry_cache__"]
+    assert cache
+    for rb, ind in cache.values():
+        assert type(rb) is ops.Rulebook and isinstance(ind, torch.Tensor)
+
+
 def test_chain_rulebooks_kitti_occupancy_and_detection_grids(mark_mode):
     from btcdet_amd import synth
     b = synth.make_batch([31, 32])

@@ -144,6 +144,31 @@ def test_det_backbone_vs_oracle_chain(M, which):
         bb.load_state_dict(saved)     # train mode moved the running statistics
 
 
+def test_det_backbone_with_and_without_the_geometry_walk(M):
+    """backbones_3d.DET_GEOMETRY_WALK: all rulebooks from one walk and the stages as compiled chains, or every layer building its own
+    rulebook synchronously and running by itself -- the maps are equal value for value and the kernels are the same, so a train-mode
+    forward gives the same bits"""
+    from btcdet_amd import backbones_3d
+    cfg, model = M
+    feats, occ, coords, bs = golden_inputs()
+    bb = model.det_modules.backbone_3d
+    saved = {k: v.clone() for k, v in bb.state_dict().items()}
+    flag = backbones_3d.DET_GEOMETRY_WALK
+    got = {}
+    try:
+        for walk in (True, False):
+            backbones_3d.DET_GEOMETRY_WALK = walk
+            out, xc, sf, _ = run_gpu(model, feats, occ, coords, bs, True)
+            got[walk] = (out.indices.clone(), out.features.clone(), xc.features.clone(), sf.clone())
+            bb.load_state_dict(saved)     # train mode moved the running statistics
+    finally:
+        backbones_3d.DET_GEOMETRY_WALK = flag
+        bb.load_state_dict(saved)
+    for name, a, b in zip(("encoded_spconv_tensor indices", "encoded_spconv_tensor features", "x_combine features", "spatial_features"),
+                          got[True], got[False]):
+        assert torch.equal(a, b), name
+
+
 @pytest.mark.parametrize("which", ["golden", "full"])
 def test_det_backbone_gradients_vs_float64_autograd(M, which):
     cfg, model = M

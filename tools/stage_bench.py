@@ -9,7 +9,6 @@ sys.path.insert(0, ROOT)
 from btcdet_amd.spconv import ops, utils
 
 dev = torch.device("cuda:0")
-ops.LOOKAHEAD = False if hasattr(ops, "LOOKAHEAD") else None
 
 
 def timed(fn, reps=10):
