@@ -77,6 +77,55 @@ int btc_det_finish(const float* cls_preds, const float* box_preds, int batch, in
                    const float* h_thresh, int n_thresh, float* pred_boxes, float* pred_scores, long long* pred_labels, float* pred_iou,
                    long long* counters, void* stream);
 
+/* ---- KITTI AP evaluation: the reference's kitti_object_eval_python (eval.py's overlaps and the two passes of compute_statistics_jit) for
+ * a whole dataset in a constant number of launches.  The ground truths, detections and DontCare boxes of ALL frames arrive concatenated,
+ * everything float64 (scores are never rounded: ties are decided on the caller's values):
+ *
+ *   gt_rows  [NG][12]  image box x1 y1 x2 y2, location x y z (camera frame, y the bottom face), dimensions l h w, rotation_y, alpha
+ *   dt_rows  [ND][13]  the same 12 and the score
+ *   dc_boxes [NC][4]   the image boxes of a frame's DontCare ground truths, in their order
+ *   frames   [n_frames + 1][3] int32  index of each frame's first ground truth / detection / DontCare box (row n_frames: NG, ND, NC)
+ *   pairs    [n_frames + 1][2] int64  exclusive prefix sums over the frames of n_dt * n_gt and of n_dt * n_dc
+ *   h_frames HOST copy of `frames`: the argument checks read it.  A frame with more than 1024 detections or more than 1024 ground
+ *            truths is BTC_EINVAL (refused, never truncated); zero frames and frames without boxes are valid.
+ *
+ * btc_kitti_overlaps -- per frame, and only within it, the [n_dt][n_gt] blocks of the three metrics, one launch:
+ *   ov    [3][P] OUT  P = pairs[n_frames][0]; metric 0 the image-box IoU (image_box_overlap, criterion -1), 1 the rotated BEV IoU of
+ *                     (x, z, l, w, rotation_y), 2 d3_box_overlap: the BEV intersection x the height overlap over the union of volumes.
+ *                     Entry pairs[f][0] + j * n_gt + i is detection j against ground truth i of frame f.
+ *   ov_dc [PD]   OUT  detection against DontCare box, the detection's area as denominator (image_box_overlap criterion 0), at
+ *                     pairs[f][1] + j * n_dc + i.
+ *   The rotated intersection is exact convex clipping in float64 (no margin, unlike the NMS kernels' box_overlap). */
+int btc_kitti_overlaps(const double* gt_rows, const double* dt_rows, const double* dc_boxes, const int32_t* frames, const long long* pairs,
+                       const int32_t* h_frames, int n_frames, double* ov, double* ov_dc, void* stream);
+
+/* The matching.  A combination is (metric, class, difficulty, overlap level), index ((m * n_class + c) * n_diff + d) * n_level + k, the
+ * metrics being metric_first .. metric_first + n_metric - 1 (0 bbox, 1 bev, 2 3d).
+ *
+ *   ign_gt [n_class * n_diff][NG] int8, ign_dt [n_class * n_diff][ND] int8: clean_data's 0 counted / 1 ignored / -1 another class
+ *   min_overlaps [n_level][3][n_class] float64
+ *
+ * btc_kitti_match_tp -- pass A (thresh = 0, compute_fp = False) of every frame and combination, a memset and one launch:
+ *   tp_det   [combinations][NG] int32 OUT  index into dt_rows of the detection ground truth g matched as a true positive, else -1
+ *   tp_count [combinations] int32     OUT  the number of true positives
+ *
+ * btc_kitti_match_stats -- pass B (compute_fp = True) of every frame, combination and threshold: memsets and two launches.
+ *   thresholds [combinations][41] float64, n_thresholds [combinations] int32 (0 .. 41): get_thresholds' list of each combination
+ *   counts     [combinations][41][3] int32 OUT  tp, fp (DontCare detections subtracted for metric 0), fn, summed over the frames
+ *   similarity [n_class * n_diff * n_level][41] float64 OUT  sum over the true positives of (1 + cos(alpha_gt - alpha_dt)) / 2 for
+ *              metric 0 when compute_aos and metric_first == 0, zeros otherwise; per-frame partials summed in frame order (same bits
+ *              every run)
+ *   ws         btc_kitti_match_stats_ws_bytes(...) bytes, contents arbitrary */
+int btc_kitti_match_tp(const double* ov, const double* dt_rows, const int8_t* ign_gt, const int8_t* ign_dt, const double* min_overlaps,
+                       const int32_t* frames, const long long* pairs, const int32_t* h_frames, int n_frames, int metric_first, int n_metric,
+                       int n_class, int n_diff, int n_level, int32_t* tp_det, int32_t* tp_count, void* stream);
+size_t btc_kitti_match_stats_ws_bytes(int n_frames, int n_class, int n_diff, int n_level, int compute_aos);
+int btc_kitti_match_stats(const double* ov, const double* ov_dc, const double* gt_rows, const double* dt_rows, const int8_t* ign_gt,
+                          const int8_t* ign_dt, const double* min_overlaps, const double* thresholds, const int32_t* n_thresholds,
+                          const int32_t* frames, const long long* pairs, const int32_t* h_frames, int n_frames, int metric_first, int n_metric,
+                          int n_class, int n_diff, int n_level, int compute_aos, int32_t* counts, double* similarity, void* ws,
+                          size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
