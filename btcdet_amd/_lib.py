@@ -187,6 +187,8 @@ _INFER_SIGS = {
     "btc_det_select_nms_ws_bytes": (sz, [ci, ci]),
     "btc_det_select_nms": (ci, [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
     "btc_det_finish": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, ci, ci, c_f32p, ci, vp, vp, vp, vp, vp, vp]),
+    "btc_occ_metrics_ws_bytes": (sz, [ci, ci]),
+    "btc_occ_metrics": (ci, [vp, vp, vp, vp, ctypes.c_longlong, vp, vp, vp, ctypes.c_longlong, vp, vp, ci, ci, ci, vp, vp, sz, vp]),
     "btc_kitti_overlaps": (ci, [vp, vp, vp, vp, vp, c_i32p, ci, vp, vp, vp]),
     "btc_kitti_match_tp": (ci, [vp, vp, vp, vp, vp, vp, vp, c_i32p, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
     "btc_kitti_match_stats_ws_bytes": (sz, [ci, ci, ci, ci, ci]),

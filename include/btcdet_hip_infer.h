@@ -77,6 +77,34 @@ int btc_det_finish(const float* cls_preds, const float* box_preds, int batch, in
                    const float* h_thresh, int n_thresh, float* pred_boxes, float* pred_scores, long long* pred_labels, float* pred_iou,
                    long long* counters, void* stream);
 
+/* ---- Occupancy metrics of an eval batch: the counts behind the reference's Detector3DTemplate.occ_post_processing (precision / recall / F1
+ * of the predicted occupancy at 0.5, and the ground-truth boxes that receive an added occupancy point at probability >= 0.1 .. 0.9) as one
+ * memset and at most TWO launches per batch, for any number of scenes, boxes and points, and no read-back.
+ *
+ * btc_occ_metrics fully overwrites one row of 16 int64 counters:
+ *
+ *   [0] total        sum of cls_mask (general_cls_loss_mask)          [1] pos_num  sum of pos_mask        [2] neg_num  sum of neg_mask
+ *   [3] pos_predict  cells with prob >= 0.5f (ALL cells: the head has multiplied prob by the mask; a NaN fails)
+ *   [4] pos_correct  cells with pos_mask set and prob >= 0.5f         [5] pos_all_num, copied through
+ *   [6] box_num_sum  sum over the scenes of gt_boxes_num              (also when there is no point)
+ *   [7 + k], k = 0 .. 8: valid boxes that contain at least one point whose probability is >= (float)((k + 1) * 0.1) -- the product in
+ *                    double, rounded to float32 once: the value torch compares a float32 tensor with.  Each scene's boxes against that
+ *                    scene's points only; a point inside several boxes counts for each of them.
+ *
+ *   prob      [n_cells] fp32          cls_mask, pos_mask, neg_mask  [n_cells] bytes, 0 / 1 (a non-zero byte counts once); ANY alignment
+ *   pos_all_num  one int32
+ *   occ_pnts  [n_points][4] fp32  x y z probability (>= 0; 16-byte aligned)      occ_b_ind [n_points] int64, the point's scene; a point whose
+ *             scene is outside 0 .. batch-1 takes no part.  n_points may be 0 (both pointers may be NULL then): counters 7 .. 15 are 0.
+ *   gt_boxes  [batch][max_boxes][gt_stride >= 7] fp32  x y z dx dy dz heading; gt_boxes_num [batch] int32, clamped to 0 .. max_boxes.  ONLY
+ *             the first gt_boxes_num[b] rows of scene b are read.  A point is inside a box when, in the box's frame, |x| <= dx / 2,
+ *             |y| <= dy / 2 and |z| <= dz / 2 (both faces inclusive).  max_boxes has no limit.
+ *   ws        btc_occ_metrics_ws_bytes(batch, max_boxes) bytes, contents arbitrary */
+size_t btc_occ_metrics_ws_bytes(int batch, int max_boxes);
+int btc_occ_metrics(const float* prob, const uint8_t* cls_mask, const uint8_t* pos_mask, const uint8_t* neg_mask, long long n_cells,
+                    const int32_t* pos_all_num, const float* occ_pnts, const long long* occ_b_ind, long long n_points, const float* gt_boxes,
+                    const int32_t* gt_boxes_num, int batch, int max_boxes, int gt_stride, long long* counters, void* ws, size_t ws_bytes,
+                    void* stream);
+
 /* ---- KITTI AP evaluation: the reference's kitti_object_eval_python (eval.py's overlaps and the two passes of compute_statistics_jit) for
  * a whole dataset in a constant number of launches.  The ground truths, detections and DontCare boxes of ALL frames arrive concatenated,
  * everything float64 (scores are never rounded: ties are decided on the caller's values):
