@@ -74,8 +74,7 @@ bool btc_apply_glds_supported(int K, int Cred, int Cres);
 bool btc_apply_glds_has_shape(int shape, bool bf = false);
 size_t btc_apply_glds_lds_bytes(int shape, int kc, int K, bool bf, int stages = 3);
 int btc_apply_glds_stages(int shape, int kc, int K, bool bf, int asked);
-// xcd: kernel flags -- bit 0 = XCD-contiguous tile mapping, bit 1 = `nbr` is a submanifold layer's forward map read as its backward
-// map (column K-1-k holds offset k: the two maps are mirror images, rulebook.hip)
+// xcd: the kernel's flags word (conv_tile.h: APPLY_XCD, APPLY_MIRROR; the ring depth is filled in by the launcher)
 int btc_launch_apply_glds(bool trans_w, int shape, int kc, int xcd, bool bf, const void* feat, const float* W, const float* bias,
                           const int32_t* nbr, const int32_t* order /* row order hint or NULL */, int n_rows, int K, int Cred, int Cres, void* out,
                           hipStream_t stream, const struct BnFuse* bn = nullptr /* bn_fuse.h: batch statistics of the result in the epilogue */);

@@ -21,27 +21,13 @@
 //     A   : TM gathered rows x KC bf16        unit p of row r holds source unit  p ^ ((r / RPB) & (UPR - 1))
 //     B^T : TN weight rows  x KC bf16         same rule
 // A lane's MFMA fragment (8 consecutive reduction channels of its row / column) is one 16-byte LDS read for each operand.
-#include <mutex>
-
-#include "btc_common.h"
-#include "bn_fuse.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "conv_tile.h"
 
 namespace {
 
 __device__ unsigned short g_zero_row_b[128];  // zero-initialised source of gathers for absent neighbours (>= KC bf16)
 
 constexpr int B_STAGES = 3;
-
-__device__ __forceinline__ void glds16b(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_b() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // PAIR (KC = 64 over a 32-channel reduction), as in conv_apply_s: an item is TWO active offsets -- units 0..3 of a 64-channel A row are
 // the row gathered for the first, 4..7 for the second; the weight panel is the two offsets' panels side by side -- so a tile walks
@@ -50,7 +36,7 @@ template <int WR, int WC, int NTW, int KC, bool PAIR = false>
 __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned short* __restrict__ feat, const unsigned short* __restrict__ Wq,
                                                              const float* __restrict__ bias, const int32_t* __restrict__ nbr,
                                                              const int32_t* __restrict__ order, int n_rows, int K, int Cred, int Cres,
-                                                             unsigned short* __restrict__ out, int xcd_swizzle, const BnFuse bn) {
+                                                             unsigned short* __restrict__ out, int flags, const BnFuse bn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = WR * WC, THREADS = 64 * NW;
   constexpr int TM = 16 * WR, TN = 16 * NTW * WC;
@@ -64,50 +50,13 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
   constexpr int B_BYTES = (TN * KC * 2 + 1023) / 1024 * 1024;
   constexpr int STAGE = A_BYTES + B_BYTES;
   char* ring = smem;
-  int32_t* s_nbr = (int32_t*)(ring + B_STAGES * STAGE);  // [TM][K]
-  int32_t* s_kact = s_nbr + TM * K;
-  int32_t* s_nact = s_kact + K;
-  int32_t* s_row = s_nact + 1;                           // [TM] row of each tile slot (order[] or identity), -1 past the end
+  APPLY_TAIL(ring + B_STAGES * STAGE, TM, K);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WC, wc = wave % WC;
-  const int mirror = (xcd_swizzle >> 1) & 1;   // bit 1: a submanifold FORWARD map read as the backward map (column K-1-k), see conv_apply_g
-  xcd_swizzle &= 1;
-  int bx = blockIdx.x;
-  if (xcd_swizzle) {
-    const int nb = gridDim.x, per = nb >> 3, main = per << 3;
-    if (bx < main) bx = (bx & 7) * per + (bx >> 3);
-  }
-  const int row0 = bx * TM;
-  const int n0 = blockIdx.y * TN;
-
-  for (int e = tid; e < K; e += THREADS) s_kact[e] = 0;
-  for (int e = tid; e < TM; e += THREADS) s_row[e] = (row0 + e < n_rows) ? (order ? order[row0 + e] : row0 + e) : -1;
-  __syncthreads();
-  for (int e = tid; e < TM * K; e += THREADS) {
-    const int rloc = e / K, kk = e - rloc * K;
-    const int gr = s_row[rloc];
-    const int v = gr >= 0 ? nbr[(long long)gr * K + (mirror ? K - 1 - kk : kk)] : -1;
-    s_nbr[e] = v;
-    if (v >= 0) s_kact[kk] = 1;
-  }
-  __syncthreads();
-  unsigned long long wave_act;
-  {
-    bool any = false;
-    if (lane < K)
-      for (int r = 0; r < 16; ++r) any |= s_nbr[(wr * 16 + r) * K + lane] >= 0;
-    wave_act = __ballot(any);
-  }
-  const int kflag = (lane < K) ? s_kact[lane] : 0;
-  __syncthreads();
-  if (wave == 0) {
-    const unsigned long long m = __ballot(kflag != 0);
-    if (kflag) s_kact[__popcll(m & ((1ull << lane) - 1ull))] = lane;
-    if (lane == 0) *s_nact = __popcll(m);
-  }
-  __syncthreads();
-  const int n_act = *s_nact;
+  const ApplyTile tile = apply_tile_prologue<TM, THREADS>(s_nbr, s_kact, s_nact, s_row, nbr, order, n_rows, K, flags, wr);
+  const int bx = tile.bx, n0 = blockIdx.y * TN, n_act = tile.n_act;
+  const unsigned long long wave_act = tile.wave_act;
   static_assert(!PAIR || KC == 64, "PAIR: two 32-channel offsets per 64-channel item");
   const int n_chunks = PAIR ? 1 : Cred / KC;
   const int n_items = PAIR ? (n_act + 1) >> 1 : n_act * n_chunks;
@@ -135,7 +84,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
         const int ku = (PAIR && (u & 4)) ? k1 : k;
         const int nb = ku >= 0 ? s_nbr[rloc * K + ku] : -1;
         const unsigned short* src = nb >= 0 ? feat + (size_t)nb * Cred + cc + (PAIR ? (u & 3) : u) * 8 : g_zero_row_b;
-        glds16b(src, As + ai * 1024);
+        glds16(src, As + ai * 1024);
       }
     }
     const unsigned short* Wk = Wq + ((size_t)k * Cres + n0) * Cred + cc;
@@ -148,7 +97,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
       if (B_UNITS % 64 == 0 || U < B_UNITS) {
         const int c = U / UPR;
         const int u = (U % UPR) ^ ((c / RPB) & (UPR - 1));
-        glds16b(((PAIR && (u & 4)) ? Wk1 : Wk) + (size_t)c * Cred + (PAIR ? (u & 3) : u) * 8, Bs + bi * 1024);
+        glds16(((PAIR && (u & 4)) ? Wk1 : Wk) + (size_t)c * Cred + (PAIR ? (u & 3) : u) * 8, Bs + bi * 1024);
       }
     }
   };
@@ -158,8 +107,8 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
   if (n_items > 1) issue(1);
   int st = 0;
   for (int item = 0; item < n_items; ++item) {
-    if (item + 1 < n_items) wait_vm_b<NPI>();
-    else wait_vm_b<0>();
+    if (item + 1 < n_items) wait_vm<NPI>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (item + 2 < n_items) issue(st == 0 ? 2 : st - 1);
@@ -194,26 +143,12 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
     st = (st == B_STAGES - 1) ? 0 : st + 1;
   }
 
-  // C/D layout of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
   float vals[NTW][4];
   bool valid[4];
-  const bool ev = bn.ev_mean != nullptr;   // (bn_fuse.h, second mode)
+  int rows[4];
 #pragma unroll
-  for (int nt = 0; nt < NTW; ++nt) {
-    const int col = n0 + (wc * NTW + nt) * 16 + (lane & 15);
-    const float bv0 = bias ? bias[col] : 0.f;
-    BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
-    if (ev) ec = bn_eval_col(bn, col);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = s_row[wr * 16 + kq * 4 + r];
-      unsigned short h = btc_f32_to_bf16(bias ? (acc[nt][r] + bv0) : acc[nt][r]);
-      if (ev) h = btc_f32_to_bf16(bn_affine(btc_bf16_to_f32(h), ec.m, ec.rs, ec.g, ec.b, bn.ev_relu));   // eval-mode BatchNorm (+ ReLU) of x as stored: y
-      if (row >= 0) out[(size_t)row * Cres + col] = h;
-      valid[r] = row >= 0;
-      vals[nt][r] = btc_bf16_to_f32(h);   // the value as STORED: what the BatchNorm behind this layer reads
-    }
-  }
+  for (int r = 0; r < 4; ++r) rows[r] = s_row[wr * 16 + kq * 4 + r];
+  apply_tile_epilogue<NTW>(acc, rows, n0 + wc * NTW * 16, bias, Cres, out, bn, bn.ev_mean != nullptr, vals, valid);
   if (bn.slots) {   // batch statistics for the BatchNorm behind this layer (bn_fuse.h), round 5: the bf16 step carried 23 bn_stats launches
     bn_fuse_wave<NTW>(bn, vals, valid, n0 + wc * NTW * 16, (int)((bx * WR + wr) & (bn.nslots - 1)));
     bn_fuse_finish(bn, (int*)smem, (double*)(smem + 16));
@@ -222,23 +157,15 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_b(const unsigned shor
 
 size_t lds_bytes_b(int tm, int tn, int kc, int K) {
   const size_t a = ((size_t)tm * kc * 2 + 1023) / 1024 * 1024, b = ((size_t)tn * kc * 2 + 1023) / 1024 * 1024;
-  return (size_t)B_STAGES * (a + b) + (size_t)(tm * K + K + 1 + tm) * sizeof(int32_t);
+  return (size_t)B_STAGES * (a + b) + apply_tail_bytes(tm, K);
 }
 
 template <int WR, int WC, int NTW, int KC, bool PAIR = false>
 int launch_b(const unsigned short* feat, const unsigned short* Wq, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,
-             int Cres, unsigned short* out, int xcd, hipStream_t stream, const BnFuse& bn) {
+             int Cres, unsigned short* out, int flags, hipStream_t stream, const BnFuse& bn) {
   constexpr int TM = 16 * WR, TN = 16 * NTW * WC;
-  const size_t lds = lds_bytes_b(TM, TN, KC, K);
-  BTC_CHECK_ARG(lds <= 160 * 1024, "conv_apply_b: tile does not fit the LDS");
-  static BtcPerDeviceOnce once;   // launches come from the training thread, the autograd thread and the prefetch thread
-  btc_once_per_device(once, [] {
-    (void)hipFuncSetAttribute((const void*)conv_apply_b<WR, WC, NTW, KC, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  dim3 grid(btc_cdiv(n_rows, TM), Cres / TN);
-  conv_apply_b<WR, WC, NTW, KC, PAIR><<<grid, 64 * WR * WC, lds, stream>>>(feat, Wq, bias, nbr, order, n_rows, K, Cred, Cres, out, xcd, bn);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  return apply_launch<conv_apply_b<WR, WC, NTW, KC, PAIR>>("conv_apply_b", dim3(btc_cdiv(n_rows, TM), Cres / TN), 64 * WR * WC, lds_bytes_b(TM, TN, KC, K),
+                                                          stream, feat, Wq, bias, nbr, order, n_rows, K, Cred, Cres, out, flags, bn);
 }
 
 template <int WR, int WC, int NTW>
@@ -259,7 +186,7 @@ int apply_b(const void* feat_, const void* Wq_, const float* bias, const int32_t
   int kc = (Cred % 64 == 0) ? 64 : 32;
   // 32-channel reductions: two offsets per 64-channel item (PAIR; BTC_TUNE_SPLIT_PAIR = 1 switches it off, same bits)
   if (Cred == 32 && K >= 8 && btc_tune_get(BTC_TUNE_SPLIT_PAIR) != 1 && (btc_tune_get(BTC_TUNE_SPLIT_PAIR) == 2 || n_rows >= 5000)) kc = 128;
-  const int xcd = (btc_tune_get(BTC_TUNE_APPLY_XCD) == 2 ? 1 : 0) | (mirror ? 2 : 0);   // kernel flags: bit 0 XCD mapping, bit 1 mirrored map
+  const int xcd = apply_flags(mirror);
   // wave shapes as conv_apply_g's policy (sparse_conv.hip): 64 rows x 128 columns on 8 waves for wide results, 16-row
   // workgroups with 4 waves across the columns when there are few rows
   if (Cres % 128 == 0) return launch_b_kc<4, 2, 4>(kc, feat, Wq, bias, nbr, order, n_rows, K, Cred, Cres, out, xcd, stream, bn);
@@ -271,21 +198,9 @@ int apply_b(const void* feat_, const void* Wq_, const float* bias, const int32_t
   return launch_b_kc<4, 1, 1>(kc, feat, Wq, bias, nbr, order, n_rows, K, Cred, Cres, out, xcd, stream, bn);
 }
 
-__global__ __launch_bounds__(256) void weights_to_bf16(const float* __restrict__ W, int K, int Cin, int Cout, unsigned short* __restrict__ w_b,
-                                                       unsigned short* __restrict__ wt_b) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long per = (long long)Cin * Cout;
-  if (e >= (long long)K * per) return;
-  const unsigned short h = btc_f32_to_bf16(W[e]);
-  w_b[e] = h;
-  const int k = (int)(e / per);
-  const int rem = (int)(e - (long long)k * per);
-  const int ci = rem / Cout, co = rem - ci * Cout;
-  wt_b[(long long)k * per + (long long)co * Cin + ci] = h;
-}
-
-// the same for up to BF16_MULTI_MAX weights in ONE launch (a parameter group's layers right behind its optimizer step: ~20 launches of 5 us
-// per step become two) -- the table travels in the kernel arguments, a block finds its weight by its first-block entry
+// W fp32 [K][Cin][Cout] -> w_b = its bf16 rounding, wt_b = the rounding of W^T [K][Cout][Cin], for up to BF16_MULTI_MAX weights in ONE launch
+// (a parameter group's layers right behind its optimizer step: ~20 launches of 5 us per step become two) -- the table travels in the
+// kernel arguments, a block finds its weight by its first-block entry
 constexpr int BF16_MULTI_MAX = 32;
 struct Bf16Table {
   const float* W[BF16_MULTI_MAX];
@@ -344,8 +259,5 @@ extern "C" int btc_conv_bf16w_supported(int K, int Cred, int Cres) { return K >=
 
 extern "C" int btc_weights_to_bf16(const float* W, int K, int Cin, int Cout, void* w_bf16, void* wt_bf16, void* stream) {
   BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1, "btc_weights_to_bf16: bad sizes");
-  const long long n = (long long)K * Cin * Cout;
-  weights_to_bf16<<<btc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(W, K, Cin, Cout, (unsigned short*)w_bf16, (unsigned short*)wt_bf16);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  return btc_weights_to_bf16_multi(&W, &w_bf16, &wt_bf16, &K, &Cin, &Cout, 1, stream);
 }

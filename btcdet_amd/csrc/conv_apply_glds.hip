@@ -12,10 +12,7 @@
 //   B fwd   [k][TN]           :  16-column group g of row k holds columns of group  g ^ (k & 1)       (conflict-free reads)
 //   B dgrad [c][KC] (= W^T)   :  slot p of column c holds reduction unit  p ^ (c & (KC/4 - 1))
 // Rows without a neighbour at the offset read a zeroed device row (the DMA has no per-lane predicated zero fill).
-#include "btc_common.h"
-#include "bn_fuse.h"
-
-#include <mutex>
+#include "conv_tile.h"
 
 namespace {
 
@@ -23,11 +20,6 @@ __device__ float g_zero_row[64];  // zero-initialised; the source of gathers for
 
 constexpr int G_STAGES_DEFAULT = 3;   // ring depth when the launcher does not say (flags bits 4..7)
 constexpr int G_STAGES_MAX = 8;
-
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16,
-                                   0, 0);
-}
 
 // 4 x 4 transpose across the four 16-lane rows of a wave: on entry lane (r, i) -- row r = lane >> 4 -- holds x[e] = M[r][e],
 // on exit y[e] = M[e][r].  Lane (i, kq) of an MFMA operand needs channel 4 q + kq for reduction step q: it reads the 16-byte
@@ -47,11 +39,6 @@ __device__ __forceinline__ void transpose4(const f32x4 v, float& y0, float& y1, 
   y0 = __uint_as_float(x0); y1 = __uint_as_float(x1); y2 = __uint_as_float(x2); y3 = __uint_as_float(x3);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Workgroup = WR x WC waves: WR 16-row groups (TM = 16 WR output rows) x WC column groups of NTW 16-column tiles
 // (TN = 16 NTW WC result channels).  KC: reduction channels per pipeline item (16, 32 or 64).
 // Small layers get small TM (more workgroups than CUs), wide layers split the columns over waves (more waves per SIMD
@@ -63,10 +50,10 @@ template <int WR, int WC, int NTW, bool TRANS_W, int KC, bool BF>
 __global__ __launch_bounds__(64 * WR * WC) void conv_apply_g(const void* __restrict__ feat_, const float* __restrict__ W,
                                                              const float* __restrict__ bias, const int32_t* __restrict__ nbr,
                                                              const int32_t* __restrict__ order, int n_rows, int K, int Cred, int Cres,
-                                                             void* __restrict__ out_, int xcd_swizzle, int dbg, const BnFuse bn) {
+                                                             void* __restrict__ out_, int flags, int dbg, const BnFuse bn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // ring depth (flags bits 4..7, set by the launcher which sized the LDS for it): S - 1 items are in flight while one is multiplied
-  const int S = ((xcd_swizzle >> 4) & 15) ? ((xcd_swizzle >> 4) & 15) : G_STAGES_DEFAULT;
+  const int S = ((flags >> APPLY_STAGES_SHIFT) & 15) ? ((flags >> APPLY_STAGES_SHIFT) & 15) : G_STAGES_DEFAULT;
   constexpr int NW = WR * WC, THREADS = 64 * NW;
   constexpr int TM = 16 * WR, TN = 16 * NTW * WC, NG = NTW * WC;  // NG: 16-column groups of the B image
   constexpr int ES = BF ? 2 : 4;                   // bytes per activation element
@@ -82,54 +69,14 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_g(const void* __restr
   constexpr int A_BYTES = (TM * KC * ES + 1023) / 1024 * 1024;
   constexpr int STAGE = A_BYTES + KC * TN * 4;     // bytes
   char* ring = smem;                               // [G_STAGES][ A: TM x KC activations | B: KC x TN fp32 ]
-  int32_t* s_nbr = (int32_t*)(ring + S * STAGE);  // [TM][K]
-  int32_t* s_kact = s_nbr + TM * K;                // [K] flags, then the compact list of active offsets
-  int32_t* s_nact = s_kact + K;                    // [1]
-  int32_t* s_row = s_nact + 1;                     // [TM] the row each tile slot works on (order[] or identity), -1 past the end
+  APPLY_TAIL(ring + S * STAGE, TM, K);
   const char* feat = (const char*)feat_;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WC, wc = wave % WC;
-  // bit 1 of the flags: the map is a submanifold layer's FORWARD map read as its backward map -- column K-1-k of nbr is
-  // offset k of the transposed map (rulebook.hip: the two are mirror images, so nbr_in is never materialised)
-  const int mirror = (xcd_swizzle >> 1) & 1;
-  xcd_swizzle &= 1;
-  int bx = blockIdx.x;
-  if (xcd_swizzle) {  // workgroups are dealt round-robin to the 8 XCDs: give XCD x the contiguous tile range x
-    const int nb = gridDim.x, per = nb >> 3, main = per << 3;
-    if (bx < main) bx = (bx & 7) * per + (bx >> 3);
-  }
-  const int row0 = bx * TM;
-  const int n0 = blockIdx.y * TN;
-
-  for (int e = tid; e < K; e += THREADS) s_kact[e] = 0;
-  for (int e = tid; e < TM; e += THREADS) s_row[e] = (row0 + e < n_rows) ? (order ? order[row0 + e] : row0 + e) : -1;
-  __syncthreads();
-  for (int e = tid; e < TM * K; e += THREADS) {
-    const int rloc = e / K, kk = e - rloc * K;
-    const int gr = s_row[rloc];
-    const int v = gr >= 0 ? nbr[(long long)gr * K + (mirror ? K - 1 - kk : kk)] : -1;
-    s_nbr[e] = v;
-    if (v >= 0) s_kact[kk] = 1;
-  }
-  __syncthreads();
-  // offsets this wave's 16-row group touches: lane k scans its column of the map (K <= 64)
-  unsigned long long wave_act;
-  {
-    bool any = false;
-    if (lane < K)
-      for (int r = 0; r < 16; ++r) any |= s_nbr[(wr * 16 + r) * K + lane] >= 0;
-    wave_act = __ballot(any);
-  }
-  const int kflag = (lane < K) ? s_kact[lane] : 0;
-  __syncthreads();
-  if (wave == 0) {  // compact list of the workgroup's active offsets, ascending
-    const unsigned long long m = __ballot(kflag != 0);
-    if (kflag) s_kact[__popcll(m & ((1ull << lane) - 1ull))] = lane;
-    if (lane == 0) *s_nact = __popcll(m);
-  }
-  __syncthreads();
-  const int n_act = *s_nact;
+  const ApplyTile tile = apply_tile_prologue<TM, THREADS>(s_nbr, s_kact, s_nact, s_row, nbr, order, n_rows, K, flags, wr);
+  const int bx = tile.bx, n0 = blockIdx.y * TN, n_act = tile.n_act;
+  const unsigned long long wave_act = tile.wave_act;   // offsets this wave's 16-row group touches
   const int n_chunks = Cred / KC;
   const int n_items = (dbg & 32) ? 0 : n_act * n_chunks;   // timing experiments: 32 = no item loop (prologue + epilogue only)
   if (dbg & 16) return;                                    //                     16 = prologue only
@@ -156,7 +103,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_g(const void* __restr
         const int u = (U % UPR) ^ ((rloc / RPB) & (UPR - 1));
         const int nb = s_nbr[rloc * K + k];
         const char* src = nb >= 0 ? feat + ((size_t)nb * Cred + cc) * ES + u * 16 : (const char*)g_zero_row;
-        glds16((const float*)src, (float*)(As + ai * 1024));
+        glds16(src, As + ai * 1024);
       }
     }
     const float* Wk = W + (size_t)k * Cred * Cres;
@@ -276,33 +223,14 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_apply_g(const void* __restr
     st = (st == S - 1) ? 0 : st + 1;
   }
 
-  // ---- epilogue: C/D layout of 16x16: col = lane&15, row = (lane>>4)*4 + reg
   float vals[NTW][4];
   bool valid[4];
+  int rows[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) rows[r] = s_row[wr * 16 + kq * 4 + r];
   const bool ev = !TRANS_W && bn.ev_mean != nullptr;   // (bn_fuse.h, second mode; forward instances only)
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt) {
-    const int col = n0 + (wc * NTW + nt) * 16 + (lane & 15);
-    const float bv0 = bias ? bias[col] : 0.f;
-    BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
-    if (ev) ec = bn_eval_col(bn, col);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = s_row[wr * 16 + kq * 4 + r];
-      valid[r] = row >= 0;
-      float v = bias ? (acc[nt][r] + bv0) : acc[nt][r];
-      if (BF) {
-        unsigned short h = btc_f32_to_bf16(v);
-        if (ev) h = btc_f32_to_bf16(bn_affine(btc_bf16_to_f32(h), ec.m, ec.rs, ec.g, ec.b, bn.ev_relu));   // of x as it would have been stored
-        if (row >= 0) ((unsigned short*)out_)[(size_t)row * Cres + col] = h;
-        v = btc_bf16_to_f32(h);   // the statistics below are those of the tensor as stored
-      } else {
-        if (ev) v = bn_affine(v, ec.m, ec.rs, ec.g, ec.b, bn.ev_relu);   // eval-mode BatchNorm (+ ReLU) folded in: y, not x
-        if (row >= 0) ((float*)out_)[(size_t)row * Cres + col] = v;
-      }
-      vals[nt][r] = v;
-    }
-  }
+  typedef typename std::conditional<BF, unsigned short, float>::type OUT;
+  apply_tile_epilogue<NTW>(acc, rows, n0 + wc * NTW * 16, bias, Cres, (OUT*)out_, bn, ev, vals, valid);
   if (bn.slots) {   // batch statistics for the BatchNorm behind this layer (bn_fuse.h)
     bn_fuse_wave<NTW>(bn, vals, valid, n0 + wc * NTW * 16, (int)((bx * WR + wr) & (bn.nslots - 1)));
     bn_fuse_finish(bn, (int*)smem, (double*)(smem + 16));
@@ -313,20 +241,12 @@ template <int WR, int WC, int NTW, bool TRANS_W, int KC, bool BF>
 int launch_g(const void* feat, const float* W, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,
              int Cres, void* out, int xcd, hipStream_t stream, const BnFuse& bn) {
   constexpr int TM = 16 * WR, TN = 16 * NTW * WC;
-  const int stages = btc_apply_glds_stages(WR * 100 + WC * 10 + NTW, KC, K, BF, (xcd >> 4) & 15);
-  xcd = (xcd & 15) | (stages << 4);
+  const int stages = btc_apply_glds_stages(WR * 100 + WC * 10 + NTW, KC, K, BF, (xcd >> APPLY_STAGES_SHIFT) & 15);
+  xcd = (xcd & (APPLY_XCD | APPLY_MIRROR)) | (stages << APPLY_STAGES_SHIFT);
   const size_t lds = btc_apply_glds_lds_bytes(WR * 100 + WC * 10 + NTW, KC, K, BF, stages);
-  BTC_CHECK_ARG(lds <= 160 * 1024, "conv_apply_g: tile does not fit the LDS");
-  static BtcPerDeviceOnce once;   // launches come from the training thread, the autograd thread and the prefetch thread
-  btc_once_per_device(once, [] {
-    (void)hipFuncSetAttribute((const void*)conv_apply_g<WR, WC, NTW, TRANS_W, KC, BF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  });
-  dim3 grid(btc_cdiv(n_rows, TM), Cres / TN);
-  conv_apply_g<WR, WC, NTW, TRANS_W, KC, BF><<<grid, 64 * WR * WC, lds, stream>>>(feat, W, bias, nbr, order, n_rows, K, Cred, Cres, out, xcd,
-                                                                                btc_tune_get(BTC_TUNE_APPLY_DEBUG), bn);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  return apply_launch<conv_apply_g<WR, WC, NTW, TRANS_W, KC, BF>>("conv_apply_g", dim3(btc_cdiv(n_rows, TM), Cres / TN), 64 * WR * WC, lds, stream, feat, W,
+                                                                  bias, nbr, order, n_rows, K, Cred, Cres, out, xcd,
+                                                                  btc_tune_get(BTC_TUNE_APPLY_DEBUG), bn);
 }
 
 #define G_ARGS feat, W, bias, nbr, order, n_rows, K, Cred, Cres, out, xcd, stream, bn
@@ -386,7 +306,7 @@ bool btc_apply_glds_has_shape(int shape, bool bf) {
 size_t btc_apply_glds_lds_bytes(int shape, int kc, int K, bool bf, int stages) {
   const int tm = 16 * (shape / 100), tn = 16 * ((shape / 10) % 10) * (shape % 10);
   const size_t a_bytes = ((size_t)tm * kc * (bf ? 2 : 4) + 1023) / 1024 * 1024;
-  return (size_t)(stages > 0 ? stages : G_STAGES_DEFAULT) * (a_bytes + (size_t)kc * tn * 4) + (size_t)(tm * K + K + 1 + tm) * sizeof(int32_t);
+  return (size_t)(stages > 0 ? stages : G_STAGES_DEFAULT) * (a_bytes + (size_t)kc * tn * 4) + apply_tail_bytes(tm, K);
 }
 
 // Ring depth of a launch.  An item of a narrow layer is 8-16 MFMAs a wave (0.1-0.25 us) against a DMA round trip of 1-2 us,

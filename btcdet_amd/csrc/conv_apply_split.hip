@@ -18,12 +18,7 @@
 // 16-lane groups by brute force):
 //     A    : TM rows x KC fp32          16-byte unit p of row r holds source unit  p ^ ((r ^ (r >> 3)) & (KC/4 - 1))
 //     B^T  : 3 planes x TN rows x KC bf16   unit p of row c holds source unit  p ^ ((c >> 1) & (KC/8 - 1))
-#include <mutex>
-
-#include "btc_common.h"
-#include "bn_fuse.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "conv_tile.h"
 
 namespace {
 
@@ -35,22 +30,6 @@ namespace {
 #define BTC_RSRC_ABSENT 0xFFFFFFF0u
 __device__ __forceinline__ void blds16s(__amdgpu_buffer_rsrc_t rsrc, unsigned voffset, void* l) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, voffset, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_s() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// two fp32 values -> one dword of each plane (low half = a's piece, high half = b's piece)
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ab = __float_as_uint(a), bb = __float_as_uint(b);
-  hi = __builtin_amdgcn_perm(bb, ab, 0x07060302u);
-  const float a1 = a - __uint_as_float(ab & 0xFFFF0000u), b1 = b - __uint_as_float(bb & 0xFFFF0000u);   // exact
-  const unsigned a1b = __float_as_uint(a1), b1b = __float_as_uint(b1);
-  mid = __builtin_amdgcn_perm(b1b, a1b, 0x07060302u);
-  const float a2 = a1 - __uint_as_float(a1b & 0xFFFF0000u), b2 = b1 - __uint_as_float(b1b & 0xFFFF0000u);   // exact
-  lo = __builtin_amdgcn_perm(__float_as_uint(b2), __float_as_uint(a2), 0x07060302u);
 }
 
 // LW > 0: LW extra LOADER waves per workgroup issue every LDS-DMA piece and wait for it; the WR x WC product waves never touch the
@@ -81,53 +60,18 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
   constexpr int A_BYTES = TM * KC * 4, P_BYTES = TN * KC * 2;   // one plane of the weight panel
   constexpr int STAGE = A_BYTES + 3 * P_BYTES;
   char* ring = smem;
-  int32_t* s_nbr = (int32_t*)(ring + S_STAGES * STAGE);  // [TM][K]
-  int32_t* s_kact = s_nbr + TM * K;
-  int32_t* s_nact = s_kact + K;
-  int32_t* s_row = s_nact + 1;                           // [TM] row of each tile slot (order[] or identity), -1 past the end
+  APPLY_TAIL(ring + S_STAGES * STAGE, TM, K);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool computes = LW == 0 || wave < NW, loads = LW == 0 || wave >= NW;
   const int wr = computes ? wave / WC : 0, wc = wave % WC;
   const int lid = LW ? wave - NW : wave;   // this wave's place among the issuing waves
-  const int mirror = (flags >> 1) & 1;   // a submanifold FORWARD map read as the backward map (column K-1-k), see conv_apply_g
-  const int dbg = flags >> 8;            // timing experiments (BTC_TUNE_APPLY_DEBUG, wrong results): 1 no products, 2 no loads inside the loop, 4 no weight panels, 8 no row gathers
-  int bx = blockIdx.x;
-  if (flags & 1) {
-    const int nb = gridDim.x, per = nb >> 3, main = per << 3;
-    if (bx < main) bx = (bx & 7) * per + (bx >> 3);
-  }
-  const int row0 = bx * TM;
-  const int n0 = blockIdx.y * TN;
+  const int dbg = flags >> APPLY_DEBUG_SHIFT;   // timing experiments (BTC_TUNE_APPLY_DEBUG, wrong results): 1 no products, 2 no loads inside the loop, 4 no weight panels, 8 no row gathers
+  const ApplyTile tile = apply_tile_prologue<TM, THREADS>(s_nbr, s_kact, s_nact, s_row, nbr, order, n_rows, K, flags, wr);   // (loader waves: wr = 0)
+  const int bx = tile.bx, n0 = blockIdx.y * TN;
+  const unsigned long long wave_act = tile.wave_act;
   const size_t plane = (size_t)K * Cred * Cres;   // elements between two planes of Ws
-
-  for (int e = tid; e < K; e += THREADS) s_kact[e] = 0;
-  for (int e = tid; e < TM; e += THREADS) s_row[e] = (row0 + e < n_rows) ? (order ? order[row0 + e] : row0 + e) : -1;
-  __syncthreads();
-  for (int e = tid; e < TM * K; e += THREADS) {
-    const int rloc = e / K, kk = e - rloc * K;
-    const int gr = s_row[rloc];
-    const int v = gr >= 0 ? nbr[(long long)gr * K + (mirror ? K - 1 - kk : kk)] : -1;
-    s_nbr[e] = v;
-    if (v >= 0) s_kact[kk] = 1;
-  }
-  __syncthreads();
-  unsigned long long wave_act;
-  {
-    bool any = false;
-    if (lane < K)
-      for (int r = 0; r < 16; ++r) any |= s_nbr[(wr * 16 + r) * K + lane] >= 0;
-    wave_act = __ballot(any);
-  }
-  const int kflag = (lane < K) ? s_kact[lane] : 0;
-  __syncthreads();
-  if (wave == 0) {
-    const unsigned long long m = __ballot(kflag != 0);
-    if (kflag) s_kact[__popcll(m & ((1ull << lane) - 1ull))] = lane;
-    if (lane == 0) *s_nact = __popcll(m);
-  }
-  __syncthreads();
-  const int n_act = __builtin_amdgcn_readfirstlane(*s_nact);   // (uniform: keeps the item cursors in scalar registers)
+  const int n_act = __builtin_amdgcn_readfirstlane(tile.n_act);   // (uniform: keeps the item cursors in scalar registers)
   static_assert(!PAIR || KC == 64, "PAIR: two 32-channel offsets per 64-channel item");
   const int n_chunks = PAIR ? 1 : Cred / KC;
   const int n_pairs = PAIR ? (n_act + 1) >> 1 : n_act;   // entries of the item walk's outer index
@@ -230,9 +174,9 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
     int st = 0;
     for (int item = i0; item < n_items; ++item) {
       const int left = n_items - 1 - item;
-      if (S_STAGES >= 4 && left >= 2) wait_vm_s<(S_STAGES >= 4 ? 2 : 0) * NPI>();
-      else if (S_STAGES >= 3 && left >= 1) wait_vm_s<(S_STAGES >= 3 ? 1 : 0) * NPI>();
-      else wait_vm_s<0>();
+      if (S_STAGES >= 4 && left >= 2) wait_vm<(S_STAGES >= 4 ? 2 : 0) * NPI>();
+      else if (S_STAGES >= 3 && left >= 1) wait_vm<(S_STAGES >= 3 ? 1 : 0) * NPI>();
+      else wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if (item + S_STAGES - 1 < n_items && !(dbg & 2)) issue(st == 0 ? S_STAGES - 1 : st - 1);
@@ -260,9 +204,9 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
       // this item has landed; the min(S_STAGES - 2, items left) issued behind it stay in flight
       const int left = n_items - 1 - item;
       if (LW == 0) {
-        if (S_STAGES >= 4 && left >= 2) wait_vm_s<(S_STAGES >= 4 ? 2 : 0) * NPI>();
-        else if (S_STAGES >= 3 && left >= 1) wait_vm_s<(S_STAGES >= 3 ? 1 : 0) * NPI>();
-        else wait_vm_s<0>();
+        if (S_STAGES >= 4 && left >= 2) wait_vm<(S_STAGES >= 4 ? 2 : 0) * NPI>();
+        else if (S_STAGES >= 3 && left >= 1) wait_vm<(S_STAGES >= 3 ? 1 : 0) * NPI>();
+        else wait_vm<0>();
       }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -314,10 +258,10 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
             if (PAIR && !((g * GS + j) ? act1 : act0)) continue;   // (this wave's 16 rows have nothing under that offset: as an item skipped)
             const f32x4 v0 = av[j][0], v1 = av[j][1];
             uint4 ah, am, al;
-            split2(v0[0], v0[1], ah.x, am.x, al.x);
-            split2(v0[2], v0[3], ah.y, am.y, al.y);
-            split2(v1[0], v1[1], ah.z, am.z, al.z);
-            split2(v1[2], v1[3], ah.w, am.w, al.w);
+            btc_split3(v0[0], v0[1], ah.x, am.x, al.x);
+            btc_split3(v0[2], v0[3], ah.y, am.y, al.y);
+            btc_split3(v1[0], v1[1], ah.z, am.z, al.z);
+            btc_split3(v1[2], v1[3], ah.w, am.w, al.w);
             const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah), Am = __builtin_bit_cast(bf16x8, am), Al = __builtin_bit_cast(bf16x8, al);
 #define S_MFMA(ACC, X, Y)                 \
     _Pragma("unroll") for (int nt = 0; nt < NTW; ++nt) ACC[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(X, Y[j][nt], ACC[nt], 0, 0, 0)
@@ -334,7 +278,9 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
       st = (st == S_STAGES - 1) ? 0 : st + 1;
     }
 
-    // epilogue as conv_apply_g's: C/D layout of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
+    // epilogue as apply_tile_epilogue's (conv_tile.h), over acc + (accm + accs).  This family keeps its own copy: through the shared
+    // function two instances change their register allocation, and the bar for sharing it is an unchanged allocation.
+    // C/D layout of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
     const bool ev = bn.ev_mean != nullptr;   // (bn_fuse.h, second mode; a z-split launch gets none: split_reduce applies it)
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
@@ -361,23 +307,16 @@ __global__ __launch_bounds__(64 * (WR * WC + LW)) void conv_apply_s(const float*
 }
 
 size_t lds_bytes_s(int tm, int tn, int kc, int K, int stages) {
-  return (size_t)stages * ((size_t)tm * kc * 4 + (size_t)3 * tn * kc * 2) + (size_t)(tm * K + K + 1 + tm) * sizeof(int32_t);
+  return (size_t)stages * ((size_t)tm * kc * 4 + (size_t)3 * tn * kc * 2) + apply_tail_bytes(tm, K);
 }
 
 template <int WR, int WC, int NTW, int KC, int S_STAGES, int LW = 0, bool PAIR = false>
 int launch_s(const float* feat, const unsigned short* Ws, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,
              int Cres, float* out, int flags, hipStream_t stream, const BnFuse& bn, int zsplit) {
   constexpr int TM = 16 * WR, TN = 16 * NTW * WC;
-  const size_t lds = lds_bytes_s(TM, TN, KC, K, S_STAGES);
-  BTC_CHECK_ARG(lds <= 160 * 1024, "conv_apply_s: tile does not fit the LDS");
-  static BtcPerDeviceOnce once;   // launches come from the training thread, the autograd thread and the prefetch thread
-  btc_once_per_device(once, [] {
-    (void)hipFuncSetAttribute((const void*)conv_apply_s<WR, WC, NTW, KC, S_STAGES, LW, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  dim3 grid(btc_cdiv(n_rows, TM), Cres / TN, zsplit);
-  conv_apply_s<WR, WC, NTW, KC, S_STAGES, LW, PAIR><<<grid, 64 * (WR * WC + LW), lds, stream>>>(feat, Ws, bias, nbr, order, n_rows, K, Cred, Cres, out, flags, bn);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  return apply_launch<conv_apply_s<WR, WC, NTW, KC, S_STAGES, LW, PAIR>>("conv_apply_s", dim3(btc_cdiv(n_rows, TM), Cres / TN, zsplit), 64 * (WR * WC + LW),
+                                                                        lds_bytes_s(TM, TN, KC, K, S_STAGES), stream, feat, Ws, bias, nbr, order, n_rows, K,
+                                                                        Cred, Cres, out, flags, bn);
 }
 
 // out[r][c] = bias[c] + slab_0[r][c] + slab_1[r][c] + ... (in that order: deterministic) of a z-split launch, with the BatchNorm
@@ -438,30 +377,9 @@ __global__ __launch_bounds__(256) void split_reduce(const float* __restrict__ sl
   }
 }
 
-__global__ __launch_bounds__(256) void weights_split3(const float* __restrict__ W, int K, int Cin, int Cout, unsigned short* __restrict__ w_s,
-                                                      unsigned short* __restrict__ wt_s) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long per = (long long)Cin * Cout, n = (long long)K * per;
-  if (e >= n) return;
-  const float x = W[e];
-  const unsigned xb = __float_as_uint(x);
-  const float x1 = x - __uint_as_float(xb & 0xFFFF0000u);
-  const unsigned x1b = __float_as_uint(x1);
-  const float x2 = x1 - __uint_as_float(x1b & 0xFFFF0000u);
-  const unsigned short p[3] = {(unsigned short)(xb >> 16), (unsigned short)(x1b >> 16), (unsigned short)(__float_as_uint(x2) >> 16)};
-  const int k = (int)(e / per);
-  const int rem = (int)(e - (long long)k * per);
-  const int ci = rem / Cout, co = rem - ci * Cout;
-  const long long et = (long long)k * per + (long long)co * Cin + ci;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    w_s[j * n + e] = p[j];
-    wt_s[j * n + et] = p[j];
-  }
-}
-
-// the same for up to SPLIT_MULTI_MAX weights in ONE launch: the table travels in the kernel arguments, a block finds its weight by
-// its first-block entry (one optimizer group's eligible layers after its step: ~10 launches of 6 us become one)
+// W fp32 [K][Cin][Cout] -> the three planes of W (w_s) and of W^T [K][Cout][Cin] (wt_s), for up to SPLIT_MULTI_MAX weights in ONE launch:
+// the table travels in the kernel arguments, a block finds its weight by its first-block entry (one optimizer group's eligible layers
+// after its step: ~10 launches of 6 us become one)
 constexpr int SPLIT_MULTI_MAX = 32;
 struct SplitTable {
   const float* W[SPLIT_MULTI_MAX];
@@ -478,12 +396,8 @@ __global__ __launch_bounds__(256) void weights_split3_multi(const SplitTable t) 
   const int Cin = t.Cin[s], Cout = t.Cout[s];
   const long long per = (long long)Cin * Cout, n = (long long)t.K[s] * per;
   if (e >= n) return;
-  const float x = t.W[s][e];
-  const unsigned xb = __float_as_uint(x);
-  const float x1 = x - __uint_as_float(xb & 0xFFFF0000u);
-  const unsigned x1b = __float_as_uint(x1);
-  const float x2 = x1 - __uint_as_float(x1b & 0xFFFF0000u);
-  const unsigned short p[3] = {(unsigned short)(xb >> 16), (unsigned short)(x1b >> 16), (unsigned short)(__float_as_uint(x2) >> 16)};
+  const BtcSplit3 x = btc_split3(t.W[s][e]);
+  const unsigned short p[3] = {(unsigned short)(x.hi >> 16), (unsigned short)(x.mid >> 16), (unsigned short)(x.lo >> 16)};
   const int k = (int)(e / per);
   const int rem = (int)(e - (long long)k * per);
   const int ci = rem / Cout, co = rem - ci * Cout;
@@ -546,7 +460,7 @@ int btc_apply_split(const float* src, const void* Ws_, const float* bias_, const
   BTC_CHECK_ARG(btc_conv_split_supported(K, Cred, Cres), "conv_apply_s: needs K <= 64, Cred %% 32 == 0, Cres %% 64 == 0 (K=%d, %d -> %d)", K, Cred, Cres);
   const BnFuse bn = bn_ ? *bn_ : btc_bn_fuse_none();
   const unsigned short* Ws = (const unsigned short*)Ws_;
-  const int flags = (btc_tune_get(BTC_TUNE_APPLY_XCD) == 2 ? 1 : 0) | (mirror ? 2 : 0) | (btc_tune_get(BTC_TUNE_APPLY_DEBUG) << 8);
+  const int flags = apply_flags(mirror) | (btc_tune_get(BTC_TUNE_APPLY_DEBUG) << APPLY_DEBUG_SHIFT);
   const int t_nt = btc_tune_get(BTC_TUNE_APPLY_NT);
   // shapes / chunk from tools/conv_bench.py on MI355X (us per launch, exact fp32 chain -> this kernel): 256 -> 128 at 14 K rows 333 -> 200
   // (64 x 128 tile, 64-channel items, double buffer; 32-channel items with three stages 241), 128 -> 128 164 -> 102, 64 -> 64 at 14 K rows
@@ -689,8 +603,5 @@ int btc_apply_split(const float* src, const void* Ws_, const float* bias_, const
 
 extern "C" int btc_weights_split3(const float* W, int K, int Cin, int Cout, void* w_split, void* wt_split, void* stream) {
   BTC_CHECK_ARG(K >= 1 && Cin >= 1 && Cout >= 1, "btc_weights_split3: bad sizes");
-  const long long n = (long long)K * Cin * Cout;
-  weights_split3<<<btc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(W, K, Cin, Cout, (unsigned short*)w_split, (unsigned short*)wt_split);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  return btc_weights_split3_multi(&W, &w_split, &wt_split, &K, &Cin, &Cout, 1, stream);
 }

@@ -24,9 +24,8 @@
 #include <type_traits>
 #include <utility>
 
-#include "btc_common.h"
+#include "conv_tile.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -38,17 +37,6 @@ constexpr int TMX = 64;   // rows per tile: two 32-row MFMA steps
 // (btc_wgrad_x_supported's callers fall back to conv_wgrad_rows_p), an offset past num_records returns zeros without a fetch
 #define X_RECORDS 0xFFFFFF00u
 #define X_ABSENT 0xFFFFFFF0u
-
-// two fp32 values -> one dword of each plane (low half = a's piece, high half = b's piece); exact (conv_apply_split.hip)
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ab = __float_as_uint(a), bb = __float_as_uint(b);
-  hi = __builtin_amdgcn_perm(bb, ab, 0x07060302u);
-  const float a1 = a - __uint_as_float(ab & 0xFFFF0000u), b1 = b - __uint_as_float(bb & 0xFFFF0000u);
-  const unsigned a1b = __float_as_uint(a1), b1b = __float_as_uint(b1);
-  mid = __builtin_amdgcn_perm(b1b, a1b, 0x07060302u);
-  const float a2 = a1 - __uint_as_float(a1b & 0xFFFF0000u), b2 = b1 - __uint_as_float(b1b & 0xFFFF0000u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(b2), __float_as_uint(a2), 0x07060302u);
-}
 
 // the lane's 8 reduction rows of one channel: two transposing reads 16 image rows apart
 template <int RS>
@@ -198,10 +186,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
     for (int s = 0; s < 2; ++s) {
       uint4 h, m, l;
       if (MODE) {
-        split2(bnf[8 * s + 0], bnf[8 * s + 1], h.x, m.x, l.x);
-        split2(bnf[8 * s + 2], bnf[8 * s + 3], h.y, m.y, l.y);
-        split2(bnf[8 * s + 4], bnf[8 * s + 5], h.z, m.z, l.z);
-        split2(bnf[8 * s + 6], bnf[8 * s + 7], h.w, m.w, l.w);
+        btc_split3(bnf[8 * s + 0], bnf[8 * s + 1], h.x, m.x, l.x);
+        btc_split3(bnf[8 * s + 2], bnf[8 * s + 3], h.y, m.y, l.y);
+        btc_split3(bnf[8 * s + 4], bnf[8 * s + 5], h.z, m.z, l.z);
+        btc_split3(bnf[8 * s + 6], bnf[8 * s + 7], h.w, m.w, l.w);
         bm[s] = __builtin_bit_cast(bf16x8, m);
         bl[s] = __builtin_bit_cast(bf16x8, l);
       } else {
@@ -246,8 +234,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
         char* d = A + kb * NPL * IMG + r * RS;
         if (MODE) {
           uint2 h, m, l;
-          split2(__uint_as_float(gq[SET][u].x), __uint_as_float(gq[SET][u].y), h.x, m.x, l.x);
-          split2(__uint_as_float(gq[SET][u].z), __uint_as_float(gq[SET][u].w), h.y, m.y, l.y);
+          btc_split3(__uint_as_float(gq[SET][u].x), __uint_as_float(gq[SET][u].y), h.x, m.x, l.x);
+          btc_split3(__uint_as_float(gq[SET][u].z), __uint_as_float(gq[SET][u].w), h.y, m.y, l.y);
           *reinterpret_cast<uint2*>(d + c * 8) = h;
           *reinterpret_cast<uint2*>(d + IMG + c * 8) = m;
           *reinterpret_cast<uint2*>(d + 2 * IMG + c * 8) = l;

@@ -12,10 +12,7 @@
 // moves (pairs * Cin + Cout) * 4 B and does 2 * pairs * Cin * Cout flop.
 //
 // Forward, data gradient, max-pool and to-dense live here; the weight gradient is in conv_wgrad.hip.
-#include <mutex>
-
-#include "btc_common.h"
-#include "bn_fuse.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -187,26 +184,13 @@ __global__ __launch_bounds__(THREADS) void conv_apply(const float* __restrict__ 
     }
   }
 
-  // ---- epilogue: C/D layout of 16x16: col = lane&15, row = (lane>>4)*4 + reg
   float vals[NT][4];
   bool valid[4];
+  int rows[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) rows[r] = row0 + wave * 16 + kq * 4 + r < n_rows ? row0 + wave * 16 + kq * 4 + r : -1;
   const bool ev = !TRANS_W && bn.ev_mean != nullptr;   // (bn_fuse.h, second mode; forward instances only)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) valid[r] = row0 + wave * 16 + kq * 4 + r < n_rows;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + nt * 16 + (lane & 15);
-    const float bv0 = (bias && col < Cres) ? bias[col] : 0.f;
-    BnEvalCol ec = {0.f, 0.f, 1.f, 0.f};
-    if (ev) ec = bn_eval_col(bn, col);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = row0 + wave * 16 + kq * 4 + r;
-      vals[nt][r] = bias ? (acc[nt][r] + bv0) : acc[nt][r];
-      if (ev) vals[nt][r] = bn_affine(vals[nt][r], ec.m, ec.rs, ec.g, ec.b, bn.ev_relu);   // eval-mode BatchNorm (+ ReLU) folded in: y, not x
-      if (col < Cres && row < n_rows) out[(size_t)row * Cres + col] = vals[nt][r];
-    }
-  }
+  apply_tile_epilogue<NT, true>(acc, rows, n0, bias, Cres, out, bn, ev, vals, valid);
   if (bn.slots) {
     bn_fuse_wave<NT>(bn, vals, valid, n0, (int)((blockIdx.x * (THREADS / 64) + wave) & (bn.nslots - 1)));
     bn_fuse_finish(bn, (int*)smem, (double*)(smem + 16));
@@ -332,6 +316,8 @@ __global__ __launch_bounds__(WS_WAVES * 64) void conv_apply_ws(const float* __re
     }
 #undef WS_FETCH
 #undef WS_MATH
+    // (this family keeps its own epilogue: through apply_tile_epilogue the two-tile instances allocate 3 registers fewer, and the bar for
+    // sharing it is an unchanged allocation)
     float vals[NT][4];
     bool valid[4];
     constexpr bool ev = EV;
@@ -407,20 +393,20 @@ __global__ __launch_bounds__(256) void dense_bwd_k(const float* __restrict__ dde
   dfeat[(size_t)i * C + c] = ddense[((size_t)q.x * C + c) * vol + ((size_t)q.y * H + q.z) * Wd + q.w];
 }
 
+// (the map tile is TM x K int32: past ~148 offsets a launch wants more than 64 KB of LDS, K = BTC_CONV_K_MAX: 157 KB.  Through
+// apply_launch every instance raises its limit on its first launch per device, not only the launches that need it.)
 template <int NT, bool TRANS_W, int THREADS>
-void launch_apply_t(dim3 grid, size_t lds, hipStream_t stream, bool vec, const float* feat, const float* W, const float* bias,
-                    const int32_t* nbr, int n_rows, int K, int Cred, int Cres, float* out, int mirror, const BnFuse& bn) {
-  // the map tile is TM x K int32: past ~148 offsets the launch wants more than 64 KB of LDS (K = BTC_CONV_K_MAX: 157 KB).  Only such
-  // launches ask for the larger limit; the configured layers (K <= 27) never reach this branch.
-  if (lds > 64 * 1024) {
-    static BtcPerDeviceOnce once;
-    btc_once_per_device(once, [] {
-      (void)hipFuncSetAttribute((const void*)conv_apply<NT, TRANS_W, true, 1, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_apply<NT, TRANS_W, false, 1, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-  }
-  if (vec) conv_apply<NT, TRANS_W, true, 1, THREADS><<<grid, THREADS, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
-  else conv_apply<NT, TRANS_W, false, 1, THREADS><<<grid, THREADS, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+int launch_apply_t(dim3 grid, size_t lds, hipStream_t stream, bool vec, const float* feat, const float* W, const float* bias,
+                   const int32_t* nbr, int n_rows, int K, int Cred, int Cres, float* out, int mirror, const BnFuse& bn) {
+  if (vec) return apply_launch<conv_apply<NT, TRANS_W, true, 1, THREADS>>("conv_apply", grid, THREADS, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+  return apply_launch<conv_apply<NT, TRANS_W, false, 1, THREADS>>("conv_apply", grid, THREADS, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+}
+
+template <bool TRANS_W, bool EV>
+int launch_ws(int nt, int wgs, size_t lds, hipStream_t stream, const float* feat, const float* W, const float* bias, const int32_t* nbr, int n_rows,
+              int K, int Cred, int Cres, float* out, int mirror, const BnFuse& bn) {
+  if (nt == 1) return apply_launch<conv_apply_ws<1, TRANS_W, EV>>("conv_apply_ws", wgs, WS_WAVES * 64, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
+  return apply_launch<conv_apply_ws<2, TRANS_W, EV>>("conv_apply_ws", wgs, WS_WAVES * 64, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
 }
 
 template <bool TRANS_W>
@@ -434,8 +420,7 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
   BTC_CHECK_ARG(!bf || btc_apply_glds_supported(K, Cred, Cres),
                 "bf16 activations need channel counts that are multiples of 16 (K=%d, %d -> %d): convert to fp32", K, Cred, Cres);
   int nt = Cres <= 16 ? 1 : (Cres <= 32 ? 2 : (Cres <= 64 ? 4 : 8));
-  const int t_kernel = btc_tune_get(BTC_TUNE_APPLY_KERNEL), t_nt = btc_tune_get(BTC_TUNE_APPLY_NT),
-            t_xcd = btc_tune_get(BTC_TUNE_APPLY_XCD);
+  const int t_kernel = btc_tune_get(BTC_TUNE_APPLY_KERNEL), t_nt = btc_tune_get(BTC_TUNE_APPLY_NT);
   // LDS-DMA pipelined kernel (conv_apply_glds.hip) for every layer whose channel counts are multiples of 16, except the
   // 200 K-row occupancy-branch layers where the register-staged kernel below measures 5-10 % faster.  Wave shapes from
   // tools/conv_bench.py on MI355X (us per launch, register-staged -> LDS-DMA): 14 K rows 64->64: 80 -> 53, 128->128: 225 -> 158,
@@ -474,7 +459,7 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
     const int t_kc = btc_tune_get(BTC_TUNE_APPLY_KC);
     if (t_kc && Cred % t_kc == 0) kc = t_kc;
     while (kc > 16 && btc_apply_glds_lds_bytes(shape, kc, K, bf) > 160 * 1024) kc >>= 1;  // 3-stage ring + map tile
-    return btc_launch_apply_glds(TRANS_W, shape, kc, (t_xcd == 2 ? 1 : 0) | (mirror ? 2 : 0), bf, feat, W, bias, nbr, order, n_rows, K, Cred, Cres, out, stream, &bn);
+    return btc_launch_apply_glds(TRANS_W, shape, kc, apply_flags(mirror), bf, feat, W, bias, nbr, order, n_rows, K, Cred, Cres, out, stream, &bn);
   }
   // weight-stationary persistent kernel (one 16-wave workgroup per CU).  Measured on MI355X: its dword-granular register
   // gather wins 2.5x for Cred <= 8 (the dgrad of the 2/3-channel occupancy heads, the 4/6-channel input layers) and loses
@@ -487,28 +472,10 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
     // the statistics epilogue's last arriver shares the slot sums through 16 + 16 bytes x threads of (by then dead) LDS
     // (bn_fuse_finish's s_part): few offsets x few channels -- K = 8 with 4 input channels is 10 KB -- would leave it short
     if (bn.slots && lds < 16 + (size_t)16 * WS_WAVES * 64) lds = 16 + (size_t)16 * WS_WAVES * 64;
-    static BtcPerDeviceOnce once;
-    btc_once_per_device(once, [] {
-      (void)hipFuncSetAttribute((const void*)conv_apply_ws<1, TRANS_W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_apply_ws<2, TRANS_W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if constexpr (!TRANS_W) {
-      if (bn.ev_mean) {   // eval-mode BatchNorm (+ ReLU) in the epilogue: the instances compiled for it
-        static BtcPerDeviceOnce once_ev;
-        btc_once_per_device(once_ev, [] {
-          (void)hipFuncSetAttribute((const void*)conv_apply_ws<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute((const void*)conv_apply_ws<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
-        if (nt == 1) conv_apply_ws<1, false, true><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
-        else conv_apply_ws<2, false, true><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
-        BTC_LAUNCH_CHECK();
-        return BTC_OK;
-      }
+    if constexpr (!TRANS_W) {   // eval-mode BatchNorm (+ ReLU) in the epilogue: the instances compiled for it
+      if (bn.ev_mean) return launch_ws<false, true>(nt, wgs, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
     }
-    if (nt == 1) conv_apply_ws<1, TRANS_W><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
-    else conv_apply_ws<2, TRANS_W><<<wgs, WS_WAVES * 64, lds, stream>>>(feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
-    BTC_LAUNCH_CHECK();
-    return BTC_OK;
+    return launch_ws<TRANS_W, false>(nt, wgs, lds, stream, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn);
   }
   // 64 rows per workgroup (256 threads).  Measured: 32- and 16-row workgroups of this register-staged kernel are ~2x SLOWER on
   // every BtcDet layer -- each workgroup re-reads all K weight panels, so L2->LDS weight traffic scales with the number of
@@ -523,14 +490,12 @@ int launch_apply(const float* feat, const float* W, const float* bias, const int
   const bool vec = (Cred & 3) == 0;
 #define BTC_APPLY(NT_) launch_apply_t<NT_, TRANS_W, 256>(grid, lds, stream, vec, feat, W, bias, nbr, n_rows, K, Cred, Cres, out, mirror, bn)
   switch (nt) {
-    case 1: BTC_APPLY(1); break;
-    case 2: BTC_APPLY(2); break;
-    case 4: BTC_APPLY(4); break;
-    default: BTC_APPLY(8); break;
+    case 1: return BTC_APPLY(1);
+    case 2: return BTC_APPLY(2);
+    case 4: return BTC_APPLY(4);
+    default: return BTC_APPLY(8);
   }
 #undef BTC_APPLY
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
 }
 
 // split operands: the kernel gathers through 32-bit byte offsets -- the HOST refuses a source it cannot reach (or whose size it was not

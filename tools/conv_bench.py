@@ -1,6 +1,7 @@
 """A/B timing of the sparse-conv apply kernel variants on the real layers of one hot-path step (tuning helper).
 
 usage: python tools/conv_bench.py [variant ...]   variant = kernel:nt:xcd (btc_tune_set values; 0 = built-in policy)
+                                                  split[:tune...] = split operands, bf16[:tune...] = bf16 operands, where they apply
 Every variant's output is compared bit-for-bit with the first one."""
 import os, sys
 import numpy as np, torch
@@ -19,6 +20,9 @@ def parse_variant(v):
     if v.startswith("split"):     # split[:tune...]: the split-operand kernel where it applies (operands = 3), tune values after the colon
         vals.append(1)
         v = v[6:] or "0"
+    elif v.startswith("bf16"):    # bf16[:tune...]: bf16 activations and the bf16 weight copies (operands = 2) where conv_apply_b takes the layer
+        vals.append(2)
+        v = v[5:] or "0"
     for i, part in enumerate(v.split(":")):
         if "=" in part:
             k, x = part.split("=")
@@ -91,7 +95,8 @@ for feats, w, b, mf, mb in cap:
         us, ref = [], None
         for v in variants:
             tune(v)
-            split = len(v) > 24 and direction != "wgrad" and L.btc_conv_split_supported(K, cin if direction == "fwd" else cout, cout if direction == "fwd" else cin) == 1
+            bf = len(v) > 24 and v[24] == 2 and direction != "wgrad" and L.btc_conv_bf16w_supported(K, cin if direction == "fwd" else cout, cout if direction == "fwd" else cin) == 1
+            split = len(v) > 24 and v[24] == 1 and direction != "wgrad" and L.btc_conv_split_supported(K, cin if direction == "fwd" else cout, cout if direction == "fwd" else cin) == 1
             if split:
                 if "planes" not in ws_cache:
                     q = torch.empty((2, 3) + tuple(w.shape), dtype=torch.bfloat16, device=dev)
@@ -104,6 +109,19 @@ for feats, w, b, mf, mb in cap:
                 else:
                     fn = lambda: check(L.btc_conv_apply_src(1, 3, ptr(dout), int(dout.shape[0]), ptr(q[0]), None, ptr(mb), None, n_src, K, cin, cout, ptr(din), stream_ptr()), "dgrad split")
                     res = din
+            elif bf:
+                if "bf16" not in ws_cache:
+                    qb = torch.empty((2,) + tuple(w.shape), dtype=torch.bfloat16, device=dev)
+                    check(L.btc_weights_to_bf16(ptr(w), K, cin, cout, ptr(qb[0]), ptr(qb[1]), stream_ptr()), "to_bf16")
+                    ws_cache["bf16"] = (qb, feats.bfloat16(), dout.bfloat16(), torch.empty((n_res, cout), dtype=torch.bfloat16, device=dev),
+                                        torch.empty((n_src, cin), dtype=torch.bfloat16, device=dev))
+                qb, feats_b, dout_b, out_b, din_b = ws_cache["bf16"]
+                if direction == "fwd":
+                    fn = lambda: check(L.btc_conv_apply_src(0, 2, ptr(feats_b), int(feats_b.shape[0]), ptr(qb[1]), ptr(b), ptr(mf), None, n_res, K, cin, cout, ptr(out_b), stream_ptr()), "fwd bf16")
+                    res = out_b
+                else:
+                    fn = lambda: check(L.btc_conv_apply_src(1, 2, ptr(dout_b), int(dout_b.shape[0]), ptr(qb[0]), None, ptr(mb), None, n_src, K, cin, cout, ptr(din_b), stream_ptr()), "dgrad bf16")
+                    res = din_b
             elif direction == "fwd":
                 fn = lambda: check(L.btc_conv_fwd(ptr(feats), ptr(w), ptr(b), ptr(mf), n_res, K, cin, cout, ptr(out), stream_ptr()), "fwd")
                 res = out
@@ -132,7 +150,9 @@ for feats, w, b, mf, mb in cap:
                 print("      vs fp64: %-12s max |err| / scale %.2e   rms err / rms %.2e" % (
                     "split" if split else "exact chain", float((cur.double() - r64).abs().max() / r64.abs().max()),
                     float((cur.double() - r64).pow(2).mean().sqrt() / r64.pow(2).mean().sqrt())))
-            if split:
+            if bf or ref.dtype != cur.dtype:
+                ok = bool((ref.float() - cur.float()).abs().max() <= 2.0 ** -6 * ref.float().abs().max())
+            elif split:
                 err = float((ref - cur).abs().max() / ref.abs().max())
                 ok = err <= 2e-6
                 worst_split = max(globals().get("worst_split", 0.0), err)
