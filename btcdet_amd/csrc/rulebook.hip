@@ -22,8 +22,8 @@
 // an open-addressing hash with 64-bit cell keys instead.
 //
 // A whole chain of layers (an encoder / decoder branch) is built in two phases around ONE read-back (btc_chain_levels /
-// btc_chain_maps): phase A builds every level on the device, each level's row count staying in device memory and the rows
-// of level l marking level l+1 with their count read from device memory; the host reads all counts at once, sizes the maps,
+// btc_chain_maps): phase A builds every level on the device, each level's row count staying in device memory and level
+// l + 1 marked from level l's bitmap, which needs neither its rows nor their count; the host reads all counts at once, sizes the maps,
 // and phase B fills every neighbour map of the chain in one multi-job launch.
 #include "btc_common.h"
 
@@ -47,21 +47,43 @@ __host__ __device__ __forceinline__ long long lvl_cell(const Level& L, int b, in
   return (long long)b * L.vol + ((long long)z * L.shape[1] + y) * L.shape[2] + x;
 }
 
-// rank of a cell of a scanned level, -1 if the cell is not active
-__device__ __forceinline__ int lvl_rank(const Level& L, long long cell) {
-  const long long w = cell >> 5;
-  const unsigned bit = (unsigned)cell & 31u;
-  const unsigned word = L.words[w];
-  if (!((word >> bit) & 1u)) return -1;
+// cell index -> (b, z, y, x)
+__device__ __forceinline__ void cell_coords(const Level& L, long long cell, int* b, int* z, int* y, int* x) {
+  const int hw = L.shape[1] * L.shape[2];
+  const int bb = (int)(cell / L.vol);
+  const int rem = (int)(cell - (long long)bb * L.vol);
+  const int zz = rem / hw;
+  const int r2 = rem - zz * hw;
+  const int yy = r2 / L.shape[2];
+  *b = bb; *z = zz; *y = yy; *x = r2 - yy * L.shape[2];
+}
+
+// rank of the first bit of word w of a scanned level = chunk prefix + block prefix + the words in front of it inside its 32-byte
+// block (one 32-byte load + two prefix words); *word = the word itself, for a caller that has not read it yet
+__device__ __forceinline__ int rank_base(const Level& L, long long w, unsigned* word) {
   const long long blk = w >> 3;
   const int wi = (int)(w & 7);
   const uint4* p = reinterpret_cast<const uint4*>(L.words + blk * RB_BLK);
   const uint4 a = p[0], b = p[1];
   const unsigned ws[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  int r = L.cprefix[blk / RB_CHUNK] + L.bprefix[blk] + __popc(word & ((1u << bit) - 1u));
+  int r = L.cprefix[blk / RB_CHUNK] + L.bprefix[blk];
+  unsigned wd = 0;
 #pragma unroll
-  for (int j = 0; j < 7; ++j) r += (j < wi) ? __popc(ws[j]) : 0;
+  for (int q = 0; q < 8; ++q) {
+    r += (q < wi) ? __popc(ws[q]) : 0;
+    wd = (q == wi) ? ws[q] : wd;
+  }
+  *word = wd;
   return r;
+}
+
+// rank of a cell of a scanned level, -1 if the cell is not active (the bit test mostly fails: it reads the one word only)
+__device__ __forceinline__ int lvl_rank(const Level& L, long long cell) {
+  const unsigned bit = (unsigned)cell & 31u;
+  const unsigned word = L.words[cell >> 5];
+  if (!((word >> bit) & 1u)) return -1;
+  unsigned same;
+  return rank_base(L, cell >> 5, &same) + __popc(word & ((1u << bit) - 1u));
 }
 
 // integer division by the small runtime constants of a geometry is ~40 instructions on this ISA: the common values
@@ -90,23 +112,66 @@ __device__ __forceinline__ void split_item(long long t, int K, int* i, int* kk) 
   else { const long long q = t / K; *i = (int)q; *kk = (int)(t - q * K); }
 }
 
-// one axis of the forward map: input coordinate + kernel offset -> output coordinate (CONV: divisibility; TRANSPOSE: integral)
-__device__ __forceinline__ bool fwd_axis(const BtcGeom& g, int j, int c, int kv, int* o) {
+// ---- the axis map: ONE statement of how a walked cell + a kernel offset reach a cell of the target level, for the three directions
+//   JOB_FWD   cells of a layer's input level  -> its output level
+//   JOB_BWD   cells of a layer's output level -> its input level
+//   JOB_SUBM  cells of a level -> the same level (centred kernel)
+// (the marks are JOB_FWD with a constant direction: the other branches fold away)
+enum { JOB_FWD = 0, JOB_BWD = 1, JOB_SUBM = 2 };
+
+// one axis: coordinate c of the walked cell + kernel offset kv -> coordinate in the target level, whose extent along the axis is `extent`
+__device__ __forceinline__ bool map_axis(const BtcGeom& g, int dir, int extent, int j, int c, int kv, int* o) {
   int q;
-  if (g.mode == BTC_MODE_CONV) {
+  if (dir == JOB_SUBM) {
+    q = c + (kv - g.k[j] / 2) * g.d[j];
+  } else if ((dir == JOB_FWD) == (g.mode == BTC_MODE_CONV)) {   // FWD of a conv / BWD of a transposed conv: (c + p - kv d) / s, when divisible
     const int t = c + g.p[j] - kv * g.d[j];
     if (t < 0 || !div_stride(t, g.s[j], &q)) return false;
-  } else {
+  } else {                                                      // FWD of a transposed conv / BWD of a conv: c s - p + kv d
     q = c * g.s[j] - g.p[j] + kv * g.d[j];
   }
   *o = q;
-  return q >= 0 && q < g.out_shape[j];
+  return q >= 0 && q < extent;
 }
 
-__device__ __forceinline__ bool fwd_cell(const BtcGeom& g, int z, int y, int x, int kk, int* oz, int* oy, int* ox) {
-  int kz, ky, kx;
-  split_offset(g, kk, &kz, &ky, &kx);
-  return fwd_axis(g, 0, z, kz, oz) && fwd_axis(g, 1, y, ky, oy) && fwd_axis(g, 2, x, kx, ox);
+// range of target coordinates along axis j for walked coordinates c0 <= c1, clamped to the level (lo > hi: nothing)
+__device__ __forceinline__ void map_range(const BtcGeom& g, int dir, int extent, int j, int c0, int c1, int* lo, int* hi) {
+  int a, b;
+  if (dir == JOB_SUBM) {
+    a = c0 - (g.k[j] / 2) * g.d[j];
+    b = c1 + (g.k[j] - 1 - g.k[j] / 2) * g.d[j];
+  } else if ((dir == JOB_FWD) == (g.mode == BTC_MODE_CONV)) {
+    const int t0 = c0 + g.p[j] - (g.k[j] - 1) * g.d[j];
+    a = t0 <= 0 ? 0 : t0 / g.s[j];
+    b = (c1 + g.p[j]) / g.s[j];
+  } else {
+    a = c0 * g.s[j] - g.p[j];
+    b = c1 * g.s[j] - g.p[j] + (g.k[j] - 1) * g.d[j];
+  }
+  *lo = a < 0 ? 0 : a;
+  *hi = b >= extent ? extent - 1 : b;
+}
+
+// The plane-window decision of the kernels that stage a piece of a level's bitmap in LDS (thread 0): the walked cells lie in the plane
+// (b, z) and the rows y0 .. y1 of it, so what they reach in L is, per kernel plane kz < 3, one run of bitmap words -- the target plane x
+// the y-range: w0[kz] = its first word, cnt[kz] = its length (0: that kernel plane reaches nothing).  false when the kernel has more than
+// 3 planes or a run is longer than `cap` words: the caller then works on global memory.
+__device__ __forceinline__ bool plane_windows(const BtcGeom& g, int dir, const Level& L, int b, int z, int y0, int y1, int cap, long long* w0,
+                                              int* cnt) {
+  if (g.k[0] > 3) return false;
+  int ylo, yhi;
+  map_range(g, dir, L.shape[1], 1, y0, y1, &ylo, &yhi);
+  for (int kz = 0; kz < 3; ++kz) {
+    int nz;
+    cnt[kz] = 0;
+    w0[kz] = 0;
+    if (kz >= g.k[0] || ylo > yhi || !map_axis(g, dir, L.shape[0], 0, z, kz, &nz)) continue;
+    const long long w_lo = lvl_cell(L, b, nz, ylo, 0) >> 5, w_hi = lvl_cell(L, b, nz, yhi, L.shape[2] - 1) >> 5;
+    if (w_hi - w_lo + 1 > cap) return false;
+    w0[kz] = w_lo;
+    cnt[kz] = (int)(w_hi - w_lo + 1);
+  }
+  return true;
 }
 
 __device__ __forceinline__ void or_word(unsigned* words, long long w, unsigned bits) {
@@ -118,13 +183,13 @@ __device__ __forceinline__ void or_word(unsigned* words, long long w, unsigned b
 // output cell).  The axes are resolved once each (no per-offset divisions).
 __device__ __forceinline__ void mark_line(const BtcGeom& g, const Level& out, int b, int z, int y, int x, int kz, int ky) {
   int oz, oy;
-  if (!fwd_axis(g, 0, z, kz, &oz) || !fwd_axis(g, 1, y, ky, &oy)) return;
+  if (!map_axis(g, JOB_FWD, out.shape[0], 0, z, kz, &oz) || !map_axis(g, JOB_FWD, out.shape[1], 1, y, ky, &oy)) return;
   const long long line = lvl_cell(out, b, oz, oy, 0);
   long long cur_w = -1;
   unsigned cur_bits = 0;
   for (int kx = 0; kx < g.k[2]; ++kx) {
     int ox;
-    if (!fwd_axis(g, 2, x, kx, &ox)) continue;
+    if (!map_axis(g, JOB_FWD, out.shape[2], 2, x, kx, &ox)) continue;
     const long long cell = line + ox;
     const long long w = cell >> 5;
     if (w != cur_w) {
@@ -137,93 +202,24 @@ __device__ __forceinline__ void mark_line(const BtcGeom& g, const Level& out, in
   if (cur_bits) or_word(out.words, cur_w, cur_bits);
 }
 
-// n rows: from d_n (device, the count of the producing level) when given, else n_host.  A workgroup takes MARK_ROWS consecutive
-// rows.  Rows of a level built here are sorted by cell, i.e. neighbours in space, and under a stride-2 layer ~8 of them reach the
-// same output cell: marked straight into the global bitmap, the 9 x rows device-scope atomic ORs of such a workgroup pile up on a
-// few dozen words (the 40 K-row occupancy level: 53 us for this launch).  So when the workgroup's rows lie in one (batch, z) plane
-// it ORs into an LDS window of the <= 3 output planes x the y-range the rows can reach, and flushes the non-zero words with one
-// global atomic each.  `sorted` = 0 (the chain's arbitrary-order input level) and windows that do not fit mark directly.
+// Marks the output level of one strided layer from a list of n input rows in ARBITRARY order (a single rulebook's input, the chain's
+// level 0): every (row, kernel line) item goes straight into the global bitmap through mark_line.  A workgroup takes MARK_ROWS
+// consecutive rows; the grid is sized from a host-side bound and capped (mark_grid), so the workgroups stride over the row tiles.
+// (Levels built here are sorted by cell and are marked from their bitmap by rb_mark_b, which stages its ORs in LDS windows of
+// MARK_WIN words a plane.)
 constexpr int MARK_ROWS = 32;    // x (kz, ky) lines = 288 items for 256 threads; small enough that a 3 K-row level still spreads over ~100 workgroups
-constexpr int MARK_WIN = 384;   // bitmap words per staged output plane
+constexpr int MARK_WIN = 384;   // bitmap words per staged output plane of rb_mark_b
 
-__global__ __launch_bounds__(RB_T) void rb_mark(const int4* __restrict__ idx, int n_host, const int32_t* __restrict__ d_n, BtcGeom g, Level out,
-                                                int sorted) {
-  __shared__ unsigned s_win[3][MARK_WIN];
-  __shared__ long long s_w0[3];
-  __shared__ int s_cnt[3];
-  __shared__ int s_stage;
-  const int n = d_n ? *d_n : n_host;
-  const int tid = threadIdx.x;
-  // (the grid is sized from a host-side BOUND on the level's rows, capped: the workgroups stride over the real row tiles)
-  for (int r0 = blockIdx.x * MARK_ROWS; r0 < n; r0 += gridDim.x * MARK_ROWS) {
-  const int rows = n - r0 < MARK_ROWS ? n - r0 : MARK_ROWS;
-  __syncthreads();   // the previous tile's flush has read the window
-  if (tid == 0) {
-    int stage = 0;
-    if (sorted && g.k[0] <= 3 && rows >= 8) {
-      const int4 a = idx[r0], b = idx[r0 + rows - 1];
-      if (a.x == b.x && a.y == b.y) {
-        // y-range of the output cells the rows can reach (fwd_axis over y in [a.z, b.z])
-        int ylo, yhi;
-        if (g.mode == BTC_MODE_CONV) {
-          const int t0 = a.z + g.p[1] - (g.k[1] - 1) * g.d[1];
-          ylo = t0 <= 0 ? 0 : t0 / g.s[1];
-          yhi = (b.z + g.p[1]) / g.s[1];
-        } else {
-          ylo = a.z * g.s[1] - g.p[1];
-          yhi = b.z * g.s[1] - g.p[1] + (g.k[1] - 1) * g.d[1];
-        }
-        ylo = ylo < 0 ? 0 : ylo;
-        yhi = yhi >= g.out_shape[1] ? g.out_shape[1] - 1 : yhi;
-        stage = 1;
-        for (int kz = 0; kz < 3; ++kz) {
-          int oz;
-          s_cnt[kz] = 0;
-          s_w0[kz] = 0;
-          if (kz >= g.k[0] || ylo > yhi || !fwd_axis(g, 0, a.y, kz, &oz)) continue;
-          const long long w_lo = lvl_cell(out, a.x, oz, ylo, 0) >> 5, w_hi = lvl_cell(out, a.x, oz, yhi, out.shape[2] - 1) >> 5;
-          if (w_hi - w_lo + 1 > MARK_WIN) { stage = 0; break; }
-          s_w0[kz] = w_lo;
-          s_cnt[kz] = (int)(w_hi - w_lo + 1);
-        }
-      }
-    }
-    s_stage = stage;
-  }
-  for (int e = tid; e < 3 * MARK_WIN; e += RB_T) (&s_win[0][0])[e] = 0u;
-  __syncthreads();
-  const bool staged = s_stage != 0;
+__global__ __launch_bounds__(RB_T) void rb_mark(const int4* __restrict__ idx, int n, BtcGeom g, Level out) {
   const int lines = g.k[0] * g.k[1];
-  if (!staged) {
-    for (int e = tid; e < rows * lines; e += RB_T) {
+  for (int r0 = blockIdx.x * MARK_ROWS; r0 < n; r0 += gridDim.x * MARK_ROWS) {
+    const int rows = n - r0 < MARK_ROWS ? n - r0 : MARK_ROWS;
+    for (int e = threadIdx.x; e < rows * lines; e += RB_T) {
       const int il = e / lines, l = e - il * lines;
       const int kz = l / g.k[1], ky = l - kz * g.k[1];
       const int4 c = idx[r0 + il];
       mark_line(g, out, c.x, c.y, c.z, c.w, kz, ky);
     }
-    continue;
-  }
-  for (int e = tid; e < rows * lines; e += RB_T) {
-    const int il = e / lines, l = e - il * lines;
-    const int kz = l / g.k[1], ky = l - kz * g.k[1];
-    const int4 c = idx[r0 + il];
-    int oz, oy;
-    if (!fwd_axis(g, 0, c.y, kz, &oz) || !fwd_axis(g, 1, c.z, ky, &oy)) continue;
-    const long long line = lvl_cell(out, c.x, oz, oy, 0);
-    for (int kx = 0; kx < g.k[2]; ++kx) {
-      int ox;
-      if (!fwd_axis(g, 2, c.w, kx, &ox)) continue;
-      const long long cell = line + ox;
-      atomicOr(&s_win[kz][(int)((cell >> 5) - s_w0[kz])], 1u << ((unsigned)cell & 31u));
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < 3 * MARK_WIN; e += RB_T) {
-    const int pz = e / MARK_WIN, j = e - pz * MARK_WIN;
-    if (j >= s_cnt[pz]) continue;
-    const unsigned bits = s_win[pz][j];
-    if (bits) or_word(out.words, s_w0[pz] + j, bits);
-  }
   }
 }
 
@@ -231,8 +227,11 @@ __global__ __launch_bounds__(RB_T) void rb_mark(const int4* __restrict__ idx, in
 // a row, its coordinates follow from the cell index -- so marking level l + 1 needs neither level l's rows (rb_emit) nor its ranks
 // (rb_scan): a chain's levels are marked back to back and then scanned and emitted by ONE launch each (rb_scan_all, rb_emit_all): n + 2
 // dependent launches in front of the chain's read-back instead of 3 n (round 5; the detection branch 18 -> 8).  A workgroup takes
-// MARKB_WORDS consecutive words of the input bitmap (4 threads a word); spans without a set bit leave at once.  Same LDS window as
-// rb_mark when the span lies in one (batch, z) plane -- cells of a span are neighbours in space and reach the same few output words.
+// MARKB_WORDS consecutive words of the input bitmap (4 threads a word); spans without a set bit leave at once.  Cells of a span are
+// neighbours in space, and under a stride-2 layer ~8 of them reach the same output cell: marked straight into the global bitmap, the
+// device-scope atomic ORs of such a workgroup pile up on a few dozen words (the 40 K-row occupancy level: 53 us for the launch).  So when
+// the span lies in one (batch, z) plane it ORs into an LDS window of the <= 3 output planes x the y-range it can reach (plane_windows,
+// MARK_WIN words each), and flushes the non-zero words with one global atomic each; windows that do not fit mark directly.
 // lw = log2 of the span (words per workgroup), 3..8, chosen per level by the host (markb_span): large sparse levels take 256-word spans
 // (few workgroups, most of them not empty), small dense ones 8-word spans (enough workgroups to fill the chip -- a [3, 40, 53] x 2 level
 // is 398 words).  Two phases, because the set bits of a span are unevenly spread over its words (a BEV level near the sensor is dense,
@@ -257,44 +256,17 @@ __global__ __launch_bounds__(RB_T) void rb_mark_b(Level in, long long in_ncell, 
     bits &= m << ((tid & ((1 << tshift) - 1)) * nb);
   }
   if (!__syncthreads_or(bits != 0u)) return;
-  const int hw = in.shape[1] * in.shape[2];
   const long long c0 = (long long)blockIdx.x * span * 32;
   if (tid == 0) {
-    int stage = 0;
     long long c1 = c0 + (long long)span * 32 - 1;
     if (c1 >= in_ncell) c1 = in_ncell - 1;
-    const int b0 = (int)(c0 / in.vol), b1 = (int)(c1 / in.vol);
-    const int r0 = (int)(c0 - (long long)b0 * in.vol), r1 = (int)(c1 - (long long)b1 * in.vol);
-    const int z0 = r0 / hw, z1 = r1 / hw;
+    int b0, z0, y0, x0, b1, z1, y1, x1;
+    cell_coords(in, c0, &b0, &z0, &y0, &x0);
+    cell_coords(in, c1, &b1, &z1, &y1, &x1);
     s_cnt[0] = s_cnt[1] = s_cnt[2] = 0;
     s_n = 0;
-    s_b0 = b0; s_z0 = z0; s_rp0 = r0 - z0 * hw;
-    if (g.k[0] <= 3 && b0 == b1 && z0 == z1) {
-      const int y0 = (r0 - z0 * hw) / in.shape[2], y1 = (r1 - z1 * hw) / in.shape[2];
-      int ylo, yhi;
-      if (g.mode == BTC_MODE_CONV) {
-        const int t0 = y0 + g.p[1] - (g.k[1] - 1) * g.d[1];
-        ylo = t0 <= 0 ? 0 : t0 / g.s[1];
-        yhi = (y1 + g.p[1]) / g.s[1];
-      } else {
-        ylo = y0 * g.s[1] - g.p[1];
-        yhi = y1 * g.s[1] - g.p[1] + (g.k[1] - 1) * g.d[1];
-      }
-      ylo = ylo < 0 ? 0 : ylo;
-      yhi = yhi >= g.out_shape[1] ? g.out_shape[1] - 1 : yhi;
-      stage = 1;
-      for (int kz = 0; kz < 3; ++kz) {
-        int oz;
-        s_cnt[kz] = 0;
-        s_w0[kz] = 0;
-        if (kz >= g.k[0] || ylo > yhi || !fwd_axis(g, 0, z0, kz, &oz)) continue;
-        const long long w_lo = lvl_cell(out, b0, oz, ylo, 0) >> 5, w_hi = lvl_cell(out, b0, oz, yhi, out.shape[2] - 1) >> 5;
-        if (w_hi - w_lo + 1 > MARK_WIN) { stage = 0; break; }
-        s_w0[kz] = w_lo;
-        s_cnt[kz] = (int)(w_hi - w_lo + 1);
-      }
-    }
-    s_stage = stage;
+    s_b0 = b0; s_z0 = z0; s_rp0 = y0 * in.shape[2] + x0;
+    s_stage = b0 == b1 && z0 == z1 && plane_windows(g, JOB_FWD, out, b0, z0, y0, y1, MARK_WIN, s_w0, s_cnt);
   }
   __syncthreads();
   const bool staged = s_stage != 0;
@@ -320,22 +292,16 @@ __global__ __launch_bounds__(RB_T) void rb_mark_b(Level in, long long in_ncell, 
       y = rp / in.shape[2];
       x = rp - y * in.shape[2];
     } else {
-      const long long cell = c0 + off;
-      bb = (int)(cell / in.vol);
-      const int rem = (int)(cell - (long long)bb * in.vol);
-      z = rem / hw;
-      const int r2 = rem - z * hw;
-      y = r2 / in.shape[2];
-      x = r2 - y * in.shape[2];
+      cell_coords(in, c0 + off, &bb, &z, &y, &x);
       mark_line(g, out, bb, z, y, x, kz, ky);
       continue;
     }
     int oz, oy;
-    if (!fwd_axis(g, 0, z, kz, &oz) || !fwd_axis(g, 1, y, ky, &oy)) continue;
+    if (!map_axis(g, JOB_FWD, out.shape[0], 0, z, kz, &oz) || !map_axis(g, JOB_FWD, out.shape[1], 1, y, ky, &oy)) continue;
     const long long line = lvl_cell(out, bb, oz, oy, 0);
     for (int kx = 0; kx < g.k[2]; ++kx) {
       int ox;
-      if (!fwd_axis(g, 2, x, kx, &ox)) continue;
+      if (!map_axis(g, JOB_FWD, out.shape[2], 2, x, kx, &ox)) continue;
       const long long oc = line + ox;
       atomicOr(&s_win[kz][(int)((oc >> 5) - s_w0[kz])], 1u << ((unsigned)oc & 31u));
     }
@@ -349,6 +315,26 @@ __global__ __launch_bounds__(RB_T) void rb_mark_b(Level in, long long in_ncell, 
     }
 }
 
+// ---- 64-bit-key hash of an arbitrary (unsorted) input level: key = cell + 1, 0 = empty (one memset clears bitmaps and hash)
+__device__ __forceinline__ unsigned long long rb_hash64(unsigned long long k) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdULL;
+  k ^= k >> 29;
+  return k;
+}
+
+// open-addressing insert (linear probing; key 0 = empty slot): the first thread to claim a key's slot and every later one write its value
+__device__ __forceinline__ void hash_put(unsigned long long* __restrict__ keys, int32_t* __restrict__ vals, unsigned long long mask,
+                                         unsigned long long key, int val) {
+  unsigned long long slot = rb_hash64(key) & mask;
+  while (true) {
+    const unsigned long long prev = atomicCAS(&keys[slot], 0ull, key);
+    if (prev == 0ull || prev == key) break;
+    slot = (slot + 1) & mask;
+  }
+  vals[slot] = val;
+}
+
 // Marks of SEVERAL levels from the chain's input rows in ONE launch (round 5): a run of strided CONV-mode layers, each reading the level
 // the one before built (an encoder: the detection branch's conv2 .. conv_out).  Marking is monotone -- a level is a set, bits are only
 // ever set -- so the levels need no barrier between them, only a rule for WHO carries a cell on to the next level: the thread whose
@@ -358,13 +344,6 @@ __global__ __launch_bounds__(RB_T) void rb_mark_b(Level in, long long in_ncell, 
 // level-by-level launches do, without their launch boundaries.  (Marking every level from every input ROW instead -- boxes composed per
 // axis -- is correct too and was 158 us a launch: tens of thousands of threads test and OR the same few words of the deep levels.)
 // Transposed layers are left to rb_mark_b (a decoder level is 8 x its input: the queues would not hold a tile's share).
-__device__ __forceinline__ unsigned long long rb_hash64(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 29;
-  return k;
-}
-
 constexpr int MARKM_MAX = 6;      // levels per launch
 
 struct MarkMulti {
@@ -456,16 +435,9 @@ __global__ __launch_bounds__(RB_T) void rb_mark_multi(const int4* __restrict__ i
     }
     __syncthreads();
   }
-  if (M.keys && tid < MARKM_TILE && r0 + tid < n) {   // cell -> row of the input level (as rb_hash_insert)
+  if (M.keys && tid < MARKM_TILE && r0 + tid < n) {   // cell -> row of the input level (rb_hash_insert's job)
     const int4 c = idx[r0 + tid];
-    const unsigned long long key = (unsigned long long)lvl_cell(M.l0, c.x, c.y, c.z, c.w) + 1ull;
-    unsigned long long slot = rb_hash64(key) & M.mask;
-    while (true) {
-      const unsigned long long prev = atomicCAS(&M.keys[slot], 0ull, key);
-      if (prev == 0ull || prev == key) break;
-      slot = (slot + 1) & M.mask;
-    }
-    M.vals[slot] = r0 + tid;
+    hash_put(M.keys, M.vals, M.mask, (unsigned long long)lvl_cell(M.l0, c.x, c.y, c.z, c.w) + 1ull, r0 + tid);
   }
 }
 
@@ -477,6 +449,23 @@ __device__ __forceinline__ int rb_wave_incl_scan(int v) {
     if (lane >= o) v += t;
   }
   return v;
+}
+
+// exclusive prefix of v over the workgroup's threads: wave scan, then the totals of the waves in front of mine through s_wave (RB_T / 64
+// words, which the caller must not have in use); *total = the workgroup's sum
+__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = rb_wave_incl_scan(v);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < RB_T / 64; ++w) {
+    base += (w < wave) ? s_wave[w] : 0;
+    tot += s_wave[w];
+  }
+  *total = tot;
+  return base + incl - v;
 }
 
 // one thread per 32-byte block: chunk-relative block prefixes; the LAST workgroup to arrive turns the chunk sums into
@@ -492,17 +481,9 @@ __device__ __forceinline__ void scan_chunk(const Level& L, int32_t* __restrict__
     const uint4 a = p[0], b = p[1];
     cnt = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = rb_wave_incl_scan(cnt);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < RB_T / 64; ++w) {
-    base += (w < wave) ? s_wave[w] : 0;
-    tot += s_wave[w];
-  }
-  if (blk < L.nblk) L.bprefix[blk] = base + incl - cnt;
+  int tot;
+  const int excl = block_excl_scan(cnt, s_wave, &tot);
+  if (blk < L.nblk) L.bprefix[blk] = excl;
   if (threadIdx.x == 0) {
     // (device-scope store + drained queue instead of a release fence -- which writes back the XCD L2 once per workgroup, bn_fuse.h)
     btc_st_agent(&chunk_sums[chunk], tot);
@@ -516,17 +497,10 @@ __device__ __forceinline__ void scan_chunk(const Level& L, int32_t* __restrict__
   for (int c0 = 0; c0 < nchunks; c0 += RB_T) {
     const int c = c0 + threadIdx.x;
     const int v = c < nchunks ? btc_ld_agent(&chunk_sums[c]) : 0;
-    const int inc = rb_wave_incl_scan(v);
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int b2 = 0, t2 = 0;
-#pragma unroll
-    for (int w = 0; w < RB_T / 64; ++w) {
-      b2 += (w < wave) ? s_wave[w] : 0;
-      t2 += s_wave[w];
-    }
-    if (c < nchunks) L.cprefix[c] = carry + b2 + inc - v;
+    __syncthreads();   // the round before has read s_wave
+    int t2;
+    const int excl = block_excl_scan(v, s_wave, &t2);
+    if (c < nchunks) L.cprefix[c] = carry + excl;
     carry += t2;
   }
   if (threadIdx.x == 0) {
@@ -566,30 +540,18 @@ __global__ __launch_bounds__(RB_T) void rb_scan_all(const LevelSet S) {
   scan_chunk(S.lv[j], S.chunk_sums[j], S.counter[j], S.nchunks[j], S.d_total[j], (int)blockIdx.x - S.block0[j]);
 }
 
-// rows of a scanned level in ascending cell order: one thread per bitmap word (its rank base = chunk prefix + block prefix +
-// the words in front of it inside the 32-byte block)
+// rows of a scanned level in ascending cell order: one thread per bitmap word, rows from its rank base on
 __device__ __forceinline__ void emit_word(const Level& L, long long w, int4* __restrict__ out_idx, long long cap) {
   unsigned bits = L.words[w];
   if (!bits) return;
-  const long long blk = w >> 3;
-  const int wi = (int)(w & 7);
-  const uint4* p = reinterpret_cast<const uint4*>(L.words + blk * RB_BLK);
-  const uint4 a = p[0], b = p[1];
-  const unsigned ws[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  long long row = (long long)L.cprefix[blk / RB_CHUNK] + L.bprefix[blk];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) row += (j < wi) ? __popc(ws[j]) : 0;
-  const int hw = L.shape[1] * L.shape[2];
+  unsigned same;
+  long long row = rank_base(L, w, &same);
   while (bits) {
     const int bit = __ffs(bits) - 1;
     bits &= bits - 1;
-    const long long cell = w * 32 + bit;
-    const int bb = (int)(cell / L.vol);
-    const int rem = (int)(cell - (long long)bb * L.vol);
-    const int z = rem / hw;
-    const int r2 = rem - z * hw;
-    const int y = r2 / L.shape[2], x = r2 - y * L.shape[2];
-    if (row < cap) out_idx[row] = make_int4(bb, z, y, x);
+    int b, z, y, x;
+    cell_coords(L, w * 32 + bit, &b, &z, &y, &x);
+    if (row < cap) out_idx[row] = make_int4(b, z, y, x);
     ++row;
   }
 }
@@ -607,21 +569,12 @@ __global__ __launch_bounds__(RB_T) void rb_emit_all(const LevelSet S) {
   emit_word(S.lv[j], w, S.out_idx[j], S.cap[j]);
 }
 
-// ---- 64-bit-key hash of an arbitrary (unsorted) input level: key = cell + 1, 0 = empty (one memset clears bitmaps and hash)
-
 __global__ __launch_bounds__(RB_T) void rb_hash_insert(const int4* __restrict__ idx, int n, Level L, unsigned long long mask,
                                                        unsigned long long* __restrict__ keys, int32_t* __restrict__ vals) {
   const int i = blockIdx.x * RB_T + threadIdx.x;
   if (i >= n) return;
   const int4 c = idx[i];
-  const unsigned long long key = (unsigned long long)lvl_cell(L, c.x, c.y, c.z, c.w) + 1ull;
-  unsigned long long slot = rb_hash64(key) & mask;
-  while (true) {
-    const unsigned long long prev = atomicCAS(&keys[slot], 0ull, key);
-    if (prev == 0ull || prev == key) break;
-    slot = (slot + 1) & mask;
-  }
-  vals[slot] = i;
+  hash_put(keys, vals, mask, (unsigned long long)lvl_cell(L, c.x, c.y, c.z, c.w) + 1ull, i);
 }
 
 __device__ __forceinline__ int rb_hash_find(unsigned long long key, unsigned long long mask, const unsigned long long* __restrict__ keys,
@@ -649,7 +602,6 @@ __device__ __forceinline__ int rb_hash_find(unsigned long long key, unsigned lon
 // each with the rank of its first bit, in LDS, and the rows x K probes become LDS reads (one global 32-byte block + two prefix
 // words per staged WORD instead of per hit).  Windows that do not fit (sparse levels: 64 rows spread over many grid lines) and
 // hashed levels are probed directly.
-enum { JOB_FWD = 0, JOB_BWD = 1, JOB_SUBM = 2 };
 constexpr int RB_ROWS = 32;          // rows per workgroup of rb_fill (x 27 offsets = 864 probes for 256 threads)
 constexpr int RB_WIN = 224;          // bitmap words per staged plane window
 
@@ -679,41 +631,6 @@ struct Jobs {
 };
 static_assert(sizeof(Jobs) <= 4096, "rb_fill's job table must fit the kernel argument segment");
 
-// one axis of a probe: coordinate c of the walked row + kernel offset kv -> coordinate in the probed level
-__device__ __forceinline__ bool probe_axis(const Job& J, int j, int c, int kv, int* o) {
-  const BtcGeom& g = J.g;
-  int q;
-  if (J.type == JOB_SUBM) {
-    q = c + (kv - g.k[j] / 2) * g.d[j];
-  } else if ((J.type == JOB_FWD) == (g.mode == BTC_MODE_CONV)) {   // FWD of a conv / BWD of a transposed conv: (c + p - kv d) / s
-    const int t = c + g.p[j] - kv * g.d[j];
-    if (t < 0 || !div_stride(t, g.s[j], &q)) return false;
-  } else {                                                         // FWD of a transposed conv / BWD of a conv: c s - p + kv d
-    q = c * g.s[j] - g.p[j] + kv * g.d[j];
-  }
-  *o = q;
-  return q >= 0 && q < J.lvl.shape[j];
-}
-
-// range of probed coordinates along axis j for walked coordinates c0 <= c1, clamped to the level (lo > hi: nothing)
-__device__ __forceinline__ void probe_range(const Job& J, int j, int c0, int c1, int* lo, int* hi) {
-  const BtcGeom& g = J.g;
-  int a, b;
-  if (J.type == JOB_SUBM) {
-    a = c0 - (g.k[j] / 2) * g.d[j];
-    b = c1 + (g.k[j] - 1 - g.k[j] / 2) * g.d[j];
-  } else if ((J.type == JOB_FWD) == (g.mode == BTC_MODE_CONV)) {
-    const int t0 = c0 + g.p[j] - (g.k[j] - 1) * g.d[j];
-    a = t0 <= 0 ? 0 : t0 / g.s[j];
-    b = (c1 + g.p[j]) / g.s[j];
-  } else {
-    a = c0 * g.s[j] - g.p[j];
-    b = c1 * g.s[j] - g.p[j] + (g.k[j] - 1) * g.d[j];
-  }
-  *lo = a < 0 ? 0 : a;
-  *hi = b >= J.lvl.shape[j] ? J.lvl.shape[j] - 1 : b;
-}
-
 __global__ __launch_bounds__(RB_T) void rb_fill(Jobs jobs) {
   __shared__ unsigned s_word[3][RB_WIN];
   __shared__ int32_t s_base[3][RB_WIN];
@@ -736,23 +653,9 @@ __global__ __launch_bounds__(RB_T) void rb_fill(Jobs jobs) {
   // ---- staging decision (thread 0): one plane, <= 3 kernel planes, every window fits
   if (tid == 0) {
     int stage = 0;
-    if (J.ranked && J.sorted && J.g.k[0] <= 3 && rows >= 8) {
+    if (J.ranked && J.sorted && rows >= 8) {
       const int4 a = J.idx[r0], b = J.idx[r0 + rows - 1];
-      if (a.x == b.x && a.y == b.y) {
-        int ylo, yhi;
-        probe_range(J, 1, a.z, b.z, &ylo, &yhi);
-        stage = 1;
-        for (int kz = 0; kz < 3; ++kz) {
-          int nz;
-          s_cnt[kz] = 0;
-          s_w0[kz] = 0;
-          if (kz >= J.g.k[0] || ylo > yhi || !probe_axis(J, 0, a.y, kz, &nz)) continue;
-          const long long w_lo = lvl_cell(L, a.x, nz, ylo, 0) >> 5, w_hi = lvl_cell(L, a.x, nz, yhi, L.shape[2] - 1) >> 5;
-          if (w_hi - w_lo + 1 > RB_WIN) { stage = 0; break; }
-          s_w0[kz] = w_lo;
-          s_cnt[kz] = (int)(w_hi - w_lo + 1);
-        }
-      }
+      stage = a.x == b.x && a.y == b.y && plane_windows(J.g, J.type, L, a.x, a.y, a.z, b.z, RB_WIN, s_w0, s_cnt);
     }
     s_stage = stage;
   }
@@ -763,21 +666,9 @@ __global__ __launch_bounds__(RB_T) void rb_fill(Jobs jobs) {
     for (int e = tid; e < 3 * RB_WIN; e += RB_T) {
       const int pz = e / RB_WIN, j = e - pz * RB_WIN;
       if (j >= s_cnt[pz]) continue;
-      const long long w = s_w0[pz] + j;
-      const long long blk = w >> 3;
-      const int wi = (int)(w & 7);
-      const uint4* p = reinterpret_cast<const uint4*>(L.words + blk * RB_BLK);
-      const uint4 a = p[0], b = p[1];
-      const unsigned ws[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      int r = L.cprefix[blk / RB_CHUNK] + L.bprefix[blk];
-      unsigned word = 0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        r += (q < wi) ? __popc(ws[q]) : 0;
-        word = (q == wi) ? ws[q] : word;
-      }
+      unsigned word;
+      s_base[pz][j] = rank_base(L, s_w0[pz] + j, &word);
       s_word[pz][j] = word;
-      s_base[pz][j] = r;
     }
     __syncthreads();
   }
@@ -790,7 +681,8 @@ __global__ __launch_bounds__(RB_T) void rb_fill(Jobs jobs) {
     int kz, ky, kx, z, y, x;
     split_offset(J.g, kk, &kz, &ky, &kx);
     int r = -1;
-    if (probe_axis(J, 0, c.y, kz, &z) && probe_axis(J, 1, c.z, ky, &y) && probe_axis(J, 2, c.w, kx, &x)) {
+    if (map_axis(J.g, J.type, L.shape[0], 0, c.y, kz, &z) && map_axis(J.g, J.type, L.shape[1], 1, c.z, ky, &y) &&
+        map_axis(J.g, J.type, L.shape[2], 2, c.w, kx, &x)) {
       const long long cell = lvl_cell(L, c.x, z, y, x);
       if (staged) {
         const int j = (int)((cell >> 5) - s_w0[kz]);
@@ -847,8 +739,9 @@ __global__ __launch_bounds__(256) void pairs_write(const int32_t* __restrict__ n
   }
 }
 
+// the one way to a BtcGeom: `who` names the caller's subject in the message ("rulebook", "chain: layer 3")
 int fill_geom(BtcGeom* g, const int32_t* in_shape, const int32_t* out_shape, const int32_t* k, const int32_t* s,
-              const int32_t* p, const int32_t* d, int mode) {
+              const int32_t* p, const int32_t* d, int mode, const char* who = "rulebook") {
   for (int j = 0; j < 3; ++j) {
     g->in_shape[j] = in_shape[j];
     g->out_shape[j] = out_shape ? out_shape[j] : in_shape[j];
@@ -857,7 +750,7 @@ int fill_geom(BtcGeom* g, const int32_t* in_shape, const int32_t* out_shape, con
     g->p[j] = p ? p[j] : 0;
     g->d[j] = d ? d[j] : 1;
     if (g->k[j] < 1 || g->s[j] < 1 || g->d[j] < 1 || g->in_shape[j] < 1 || g->out_shape[j] < 1) {
-      btc_set_error("rulebook: bad geometry on axis %d", j);
+      btc_set_error("%s: bad geometry on axis %d (kernel, stride, dilation and both shapes must be >= 1)", who, j);
       return BTC_EINVAL;
     }
   }
@@ -903,6 +796,22 @@ Level make_level(const LevelLayout& lo, const int32_t* shape, unsigned* words, i
   L.vol = shape[0] * shape[1] * shape[2];
   L.nblk = lo.nblk;
   return L;
+}
+
+// a level's bprefix | chunk_sums | cprefix, taken from the workspace in that order (its bitmap lies in the region the caller clears)
+Level place_level(const LevelLayout& lo, const int32_t* shape, unsigned* words, BtcCarver& cv, int32_t** chunk_sums) {
+  int32_t* bprefix = cv.take<int32_t>((size_t)lo.nblk);
+  *chunk_sums = cv.take<int32_t>((size_t)(2 * lo.nchunks + 1));
+  return make_level(lo, shape, words, bprefix, *chunk_sums);
+}
+
+// one job of rb_fill's table; hash_cap = slots of the (keys, vals) hash of a level that is not ranked, else 0
+Job make_job(int type, int n, long long first_block, const BtcGeom& g, const Level& lvl, int ranked, int sorted, const int32_t* idx, int32_t* map,
+             int32_t* map2, int32_t* first, int32_t* first2, const unsigned long long* keys, const int32_t* vals, unsigned long long hash_cap) {
+  Job J;
+  J.type = type; J.n = n; J.ranked = ranked; J.sorted = sorted; J.first_block = first_block; J.g = g; J.lvl = lvl; J.idx = (const int4*)idx;
+  J.map = map; J.map2 = map2; J.first = first; J.first2 = first2; J.keys = keys; J.vals = vals; J.mask = hash_cap ? hash_cap - 1 : 0;
+  return J;
 }
 
 int markb_span(long long nw) {   // log2 words per workgroup of rb_mark_b: about 2 K workgroups, 8..256 words each
@@ -961,9 +870,7 @@ extern "C" int btc_rulebook_subm(const int32_t* indices, int n, int batch, const
   BTC_LAUNCH_CHECK();
   Jobs jobs;
   jobs.count = 1;
-  Job& J = jobs.j[0];
-  J.type = JOB_SUBM; J.n = n; J.ranked = 0; J.sorted = 0; J.first_block = 0; J.g = g; J.lvl = L; J.idx = (const int4*)indices;
-  J.map = nbr_out; J.map2 = nbr_in; J.first = nullptr; J.first2 = nullptr; J.keys = keys; J.vals = vals; J.mask = cap - 1;
+  jobs.j[0] = make_job(JOB_SUBM, n, 0, g, L, 0, 0, indices, nbr_out, nbr_in, nullptr, nullptr, keys, vals, cap);
   rb_fill<<<btc_cdiv(n, RB_ROWS), RB_T, 0, stream>>>(jobs);
   BTC_LAUNCH_CHECK();
   return BTC_OK;
@@ -981,13 +888,10 @@ static int conv_ws_carve(int batch, const int32_t* h_out_shape, void* ws, size_t
   int rc = level_layout(batch, h_out_shape, lo);
   if (rc) return rc;
   BTC_CHECK_ARG(ws_bytes >= lo->words_bytes + lo->bprefix_bytes + lo->chunk_bytes + 256, "btc_rulebook_conv: workspace too small");
-  char* base = (char*)ws;
-  unsigned* words = (unsigned*)base;
-  *counter = (int32_t*)(base + lo->words_bytes);                     // cleared together with the words
-  int32_t* bprefix = (int32_t*)(base + lo->words_bytes + 256);
-  int32_t* chunk = (int32_t*)(base + lo->words_bytes + 256 + lo->bprefix_bytes);
-  *chunk_sums = chunk;
-  *L = make_level(*lo, h_out_shape, words, bprefix, chunk);
+  BtcCarver cv(ws);
+  unsigned* words = cv.take<unsigned>((size_t)lo->nblk * RB_BLK);
+  *counter = cv.take<int32_t>(64);                                   // 256 bytes, cleared together with the words
+  *L = place_level(*lo, h_out_shape, words, cv, chunk_sums);
   return BTC_OK;
 }
 
@@ -1007,7 +911,7 @@ extern "C" int btc_rulebook_conv_count(const int32_t* indices, int n, int batch,
   if (rc) return rc;
   BTC_HIP(hipMemsetAsync(L.words, 0, lo.words_bytes + 256, stream));
   if (n > 0) {
-    rb_mark<<<mark_grid(n), RB_T, 0, stream>>>((const int4*)indices, n, nullptr, g, L, 0);
+    rb_mark<<<mark_grid(n), RB_T, 0, stream>>>((const int4*)indices, n, g, L);
     BTC_LAUNCH_CHECK();
   }
   rb_scan<<<lo.nchunks, RB_T, 0, stream>>>(L, chunk_sums, counter, lo.nchunks, d_n_out);
@@ -1037,9 +941,7 @@ extern "C" int btc_rulebook_conv_fill(const int32_t* indices, int n, int batch, 
   if (n > 0) {
     Jobs jobs;
     jobs.count = 1;
-    Job& J = jobs.j[0];
-    J.type = JOB_FWD; J.n = n; J.ranked = 1; J.sorted = 0; J.first_block = 0; J.g = g; J.lvl = L; J.idx = (const int4*)indices;
-    J.map = nbr_in; J.map2 = nbr_out; J.first = nullptr; J.first2 = nullptr; J.keys = nullptr; J.vals = nullptr; J.mask = 0;
+    jobs.j[0] = make_job(JOB_FWD, n, 0, g, L, 1, 0, indices, nbr_in, nbr_out, nullptr, nullptr, nullptr, nullptr, 0);
     rb_fill<<<btc_cdiv(n, RB_ROWS), RB_T, 0, stream>>>(jobs);
     BTC_LAUNCH_CHECK();
   }
@@ -1055,6 +957,7 @@ struct ChainPlan {
   int lvl_in[BTC_CHAIN_MAX_LAYERS], lvl_out[BTC_CHAIN_MAX_LAYERS];   // level ids per layer
   int n_levels;                                                      // including level 0
   int producer[BTC_CHAIN_MAX_LAYERS + 1];                            // level -> layer that builds it (-1 for level 0)
+  BtcGeom g[BTC_CHAIN_MAX_LAYERS];                                   // geometry of the kind-0 / kind-1 layers (fill_geom: validated)
   bool need_hash;
 };
 
@@ -1067,6 +970,12 @@ int chain_plan(const BtcChainLayer* layers, int n_layers, ChainPlan* P) {
   int cur = 0;
   for (int i = 0; i < n_layers; ++i) {
     const BtcChainLayer& l = layers[i];
+    if (l.kind == 0 || l.kind == 1) {
+      char who[32];
+      snprintf(who, sizeof(who), "chain: layer %d", i);
+      const int rc = fill_geom(&P->g[i], l.in_shape, l.out_shape, l.k, l.s, l.p, l.d, l.mode, who);
+      if (rc) return rc;
+    }
     if (l.kind == 0) {
       BTC_CHECK_ARG((l.k[0] & 1) && (l.k[1] & 1) && (l.k[2] & 1), "chain: submanifold kernel sizes must be odd");
       P->lvl_in[i] = P->lvl_out[i] = cur;
@@ -1104,46 +1013,22 @@ struct ChainWs {
 };
 
 int chain_ws(const BtcChainLayer* layers, const ChainPlan& P, int batch, int n0, void* ws, ChainWs* W) {
-  size_t off = 0;
-  char* base = (char*)ws;
+  BtcCarver cv(ws);
+  unsigned* words[BTC_CHAIN_MAX_LAYERS + 1];
   for (int lv = 1; lv < P.n_levels; ++lv) {   // bitmaps first (zeroed region)
-    const BtcChainLayer& l = layers[P.producer[lv]];
-    int rc = level_layout(batch, l.out_shape, &W->lo[lv]);
+    int rc = level_layout(batch, layers[P.producer[lv]].out_shape, &W->lo[lv]);
     if (rc) return rc;
-    W->lv[lv].words = (unsigned*)(base + off);
-    off += W->lo[lv].words_bytes;
+    words[lv] = cv.take<unsigned>((size_t)W->lo[lv].nblk * RB_BLK);
   }
-  W->counters = (int32_t*)(base + off);
-  off += btc_align((size_t)(BTC_CHAIN_MAX_LAYERS + 1) * sizeof(int32_t));
+  W->counters = cv.take<int32_t>(BTC_CHAIN_MAX_LAYERS + 1);
   W->hash_cap = P.need_hash ? subm_hash_cap(n0) : 0;
-  W->keys = (unsigned long long*)(base + off);
-  off += btc_align((size_t)W->hash_cap * sizeof(unsigned long long));
-  W->zero_bytes = off;
-  W->vals = (int32_t*)(base + off);
-  off += btc_align((size_t)W->hash_cap * sizeof(int32_t));
-  for (int lv = 1; lv < P.n_levels; ++lv) {
-    const BtcChainLayer& l = layers[P.producer[lv]];
-    unsigned* words = W->lv[lv].words;
-    int32_t* bprefix = (int32_t*)(base + off);
-    off += W->lo[lv].bprefix_bytes;
-    int32_t* chunk = (int32_t*)(base + off);
-    off += W->lo[lv].chunk_bytes;
-    W->chunk_sums[lv] = chunk;
-    W->lv[lv] = make_level(W->lo[lv], l.out_shape, words, bprefix, chunk);
-  }
-  W->total_bytes = off;
+  W->keys = cv.take<unsigned long long>(W->hash_cap);
+  W->zero_bytes = cv.off;
+  W->vals = cv.take<int32_t>(W->hash_cap);
+  for (int lv = 1; lv < P.n_levels; ++lv)
+    W->lv[lv] = place_level(W->lo[lv], layers[P.producer[lv]].out_shape, words[lv], cv, &W->chunk_sums[lv]);
+  W->total_bytes = cv.off;
   return BTC_OK;
-}
-
-BtcGeom geom_of(const BtcChainLayer& l) {
-  BtcGeom g;
-  for (int j = 0; j < 3; ++j) {
-    g.in_shape[j] = l.in_shape[j]; g.out_shape[j] = l.out_shape[j]; g.k[j] = l.k[j];
-    g.s[j] = l.s[j]; g.p[j] = l.p[j]; g.d[j] = l.d[j];
-  }
-  g.K = l.k[0] * l.k[1] * l.k[2];
-  g.mode = l.mode;
-  return g;
 }
 
 }  // namespace
@@ -1204,7 +1089,7 @@ extern "C" int btc_chain_levels(const int32_t* indices, int n0, int batch, const
       const BtcChainLayer& l = layers[i];
       if (l.kind != 1) continue;
       if (P.lvl_in[i] != at) continue;          // (a layer that reads an earlier level: not part of the run, but does not end it either)
-      if (l.mode != BTC_MODE_CONV || l.d[0] != 1 || l.d[1] != 1 || l.d[2] != 1 || l.s[0] < 1 || l.s[1] < 1 || l.s[2] < 1) break;
+      if (l.mode != BTC_MODE_CONV || l.d[0] != 1 || l.d[1] != 1 || l.d[2] != 1) break;
       // a queue entry packs (batch, z, y, x) into 8 + 16 + 20 + 20 bits: grids or batches beyond that keep the launch-per-level marks
       if (batch > 255 || l.in_shape[0] >= (1 << 16) || l.in_shape[1] >= (1 << 20) || l.in_shape[2] >= (1 << 20) ||
           l.out_shape[0] >= (1 << 16) || l.out_shape[1] >= (1 << 20) || l.out_shape[2] >= (1 << 20)) break;
@@ -1212,13 +1097,13 @@ extern "C" int btc_chain_levels(const int32_t* indices, int n0, int batch, const
       for (int j = 0; j < 3; ++j) nsz[j] = (size[j] - 1 + l.k[j] - 1) / l.s[j] + 1;
       if ((long long)MARKM_TILE * nsz[0] * nsz[1] * nsz[2] > MARKM_QCAP) break;
       for (int j = 0; j < 3; ++j) size[j] = nsz[j];
-      M.g[M.n] = geom_of(l);
+      M.g[M.n] = P.g[i];
       M.out[M.n] = W.lv[P.lvl_out[i]];
       M.lines[M.n] = ((l.k[0] - 1) / l.s[0] + 1) * ((l.k[1] - 1) / l.s[1] + 1);
       members[M.n++] = i;
       at = P.lvl_out[i];
     }
-    if (M.n >= 2) {   // (a single level: rb_mark's per-tile path is the same work)
+    if (M.n >= 2) {   // (a single level: rb_mark does the same work)
       for (int q = 0; q < M.n; ++q) composed[members[q]] = true;
     } else {
       M.n = 0;
@@ -1253,12 +1138,12 @@ extern "C" int btc_chain_levels(const int32_t* indices, int n0, int batch, const
   for (int i = 0; i < n_layers; ++i) {
     if (layers[i].kind != 1) continue;
     const int li = P.lvl_in[i], lo = P.lvl_out[i];
-    const BtcGeom g = geom_of(layers[i]);
+    const BtcGeom& g = P.g[i];
     if (composed[i]) {
       // marked above
     } else if (li == 0) {
       if (n0 > 0) {
-        rb_mark<<<mark_grid(n0), RB_T, 0, stream>>>((const int4*)indices, n0, nullptr, g, W.lv[lo], 0);
+        rb_mark<<<mark_grid(n0), RB_T, 0, stream>>>((const int4*)indices, n0, g, W.lv[lo]);
         BTC_LAUNCH_CHECK();
       }
     } else {
@@ -1357,9 +1242,7 @@ extern "C" int btc_chain_maps(const int32_t* indices, int n0, int batch, const B
       int rc2 = flush();
       if (rc2) return rc2;
     }
-    Job& J = jobs.j[jobs.count++];
-    J.type = type; J.n = n; J.ranked = ranked; J.sorted = sorted; J.first_block = blocks; J.g = g; J.lvl = lvl; J.idx = (const int4*)idx;
-    J.map = map; J.map2 = map2; J.first = first; J.first2 = first2; J.keys = W.keys; J.vals = W.vals; J.mask = W.hash_cap ? W.hash_cap - 1 : 0;
+    jobs.j[jobs.count++] = make_job(type, n, blocks, g, lvl, ranked, sorted, idx, map, map2, first, first2, W.keys, W.vals, W.hash_cap);
     blocks += nb;
     return BTC_OK;
   };
@@ -1368,7 +1251,7 @@ extern "C" int btc_chain_maps(const int32_t* indices, int n0, int batch, const B
     if (layers[i].kind == 0 && !nbr_out[i] && !nbr_in[i]) continue;   // the caller has this submanifold layer's maps already
     BTC_CHECK_ARG(nbr_out[i] && (layers[i].kind == 0 || nbr_in[i]), "btc_chain_maps: layer %d: nbr_out (and, for a strided layer, nbr_in) required", i);
     const int li = P.lvl_in[i];
-    const BtcGeom g = geom_of(layers[i]);
+    const BtcGeom& g = P.g[i];
     if (layers[i].kind == 1) {
       const int lo = P.lvl_out[i];
       // nbr_in: the input rows probe the output level; level-0 inputs also scatter nbr_out (see above)

@@ -177,7 +177,7 @@ int btc_rulebook_conv_fill(const int32_t* indices, int n, int batch, const int32
  * input level) or reuses layer ref's rulebook (kind 3: indice_key hit or identical geometry; continues on its output level).
  *   phase A  btc_chain_levels : builds every level on the device.  out_indices[i] (kind-1 layers; capacity h_cap[i] rows from
  *            btc_chain_caps, 16 bytes a row) receives the level's rows in ascending (b,z,y,x) order, d_counts[i] its row
- *            count.  Nothing is read back; level l+1 is marked from level l's rows with their count taken from d_counts.
+ *            count.  Nothing is read back; level l+1 is marked from level l's bitmap on the device.
  *   -- the caller copies d_counts (n_layers int32) to the host and sizes the maps --
  *   phase B  btc_chain_maps   : nbr_out[i] (rows_out_i, K_i) and nbr_in[i] (rows_in_i, K_i) of every kind-0 / kind-1 layer in
  *            one multi-job launch.  A strided layer's nbr_in is written by its input rows probing the output level, its nbr_out
@@ -186,7 +186,10 @@ int btc_rulebook_conv_fill(const int32_t* indices, int n, int batch, const int32
  *            adjacent buffers to make that one fill).  A kind-0 layer's nbr_in[i] may be NULL (mirror image of nbr_out, see
  *            btc_rulebook_subm); with nbr_out[i] == nbr_in[i] == NULL the layer is skipped (the caller built that rulebook).
  * ws (btc_chain_ws_bytes) must be the same, untouched, for both phases; the phases may run on different streams as long
- * as phase B is ordered behind phase A (the detection backbone runs phase A on a side stream beside its first stage). */
+ * as phase B is ordered behind phase A (the detection backbone runs phase A on a side stream beside its first stage).
+ * Every field of a kind-0 / kind-1 layer is read: k, s, d, in_shape and out_shape must be >= 1 on every axis (a submanifold layer
+ * has s = 1, p = 0, out_shape = in_shape); every chain entry point answers BTC_EINVAL otherwise, naming layer and axis
+ * (btc_chain_ws_bytes: 0).  The geometry of kind-2 / kind-3 layers is not read. */
 #define BTC_CHAIN_MAX_LAYERS 32
 typedef struct BtcChainLayer {
   int32_t kind, ref, mode;

@@ -50,6 +50,27 @@ def test_host_only_entry_points():
     assert L.btc_occ_targets_ws_bytes(ctypes.byref(cfg)) > 2 * 209 * 157 * 9 * (9 * 4 + 3 * 4)
 
 
+def test_chain_rejects_a_layer_with_bad_geometry():
+    """a chain layer whose stride or kernel size has a 0 is an argument error at every chain entry point -- here the host-only
+    ones -- instead of reaching the kernels' divisions"""
+    from btcdet_amd import _lib
+    L = _lib.lib()
+    for field in ("s", "k"):
+        layers = (_lib.BtcChainLayer * 1)()
+        l = layers[0]
+        l.kind, l.ref, l.mode = 1, -1, 1
+        l.in_shape[:], l.out_shape[:] = [9, 16, 16], [5, 8, 8]
+        l.k[:], l.s[:], l.p[:], l.d[:] = [3] * 3, [2] * 3, [1] * 3, [1] * 3
+        cap = np.zeros(1, np.int64)
+        assert L.btc_chain_caps(ctypes.byref(layers), 1, 2, 100, cap.ctypes.data) == 0 and cap[0] > 0
+        assert L.btc_chain_ws_bytes(ctypes.byref(layers), 1, 2, 100) > 0
+        getattr(l, field)[1] = 0
+        assert L.btc_chain_caps(ctypes.byref(layers), 1, 2, 100, cap.ctypes.data) == _lib.ci(-1).value
+        msg = L.btc_last_error()
+        assert msg and b"layer 0" in msg and b"axis 1" in msg
+        assert L.btc_chain_ws_bytes(ctypes.byref(layers), 1, 2, 100) == 0
+
+
 def test_environment_switches_of_the_loader(monkeypatch):
     """BTC_TUNE="key=value,..." reaches btc_tune_set when the library is loaded (a bad entry is an error, not ignored);
     BTC_TUNE_APPLY_DEBUG -- the one key that changes results -- is refused unless BTC_ALLOW_WRONG_RESULTS is set;

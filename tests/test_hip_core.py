@@ -143,6 +143,21 @@ def test_rulebook_empty_and_single():
             np.testing.assert_array_equal(rb.nbr_out.cpu().numpy(), o_out)
 
 
+@pytest.mark.parametrize("shape", [(17, 128, 128), (17, 512, 512)], ids=["half_of_the_cells", "3_percent_of_the_cells"])
+def test_rulebook_more_input_rows_than_the_mark_grid_covers(shape):
+    """rb_mark's grid is capped at 4096 workgroups of 32 rows: beyond 131 072 input rows the workgroups stride over the row tiles.
+    On the dense grid nearly every output cell is also reached by an earlier row; on the sparse one most cells the rows past
+    131 072 reach are reached by nothing else, so a tile left unmarked changes the level"""
+    rng = np.random.default_rng(11)
+    idx = rand_indices(rng, 140000, 1, shape)            # shuffled order
+    assert idx.shape[0] > 4096 * 32
+    (o_idx, o_out, o_in, o_sh), rb = _rb_both(idx, 1, shape, 3, 2, 1, 1, "conv")
+    assert list(rb.out_shape) == list(o_sh)
+    np.testing.assert_array_equal(rb.out_indices.cpu().numpy(), o_idx)
+    np.testing.assert_array_equal(rb.nbr_out.cpu().numpy(), o_out)
+    np.testing.assert_array_equal(rb.nbr_in.cpu().numpy(), o_in)
+
+
 def test_rulebook_kitti_level_shapes_and_row_alignment():
     """conv2 and the max-pool on the same geometry must emit identical output rows (sparse_cat,
     spconv_backbone.py:869-873,972-974); both equal the oracle."""
