@@ -1,4 +1,4 @@
-"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h and include/btcdet_hip_infer.h).
+"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h and include/btcdet_hip_augment.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -197,6 +197,16 @@ _INFER_SIGS = {
 
 INFER_EXPORTED_SYMBOLS = tuple(_INFER_SIGS.keys())
 
+# the entry points of the third public header, include/btcdet_hip_augment.h (same library, same rules)
+_AUGMENT_SIGS = {
+    "btc_augment_ws_bytes": (sz, [ci, ci, ci]),
+    "btc_augment_batch": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, ctypes.c_longlong, vp, vp, vp, vp, ci, ctypes.c_longlong, vp, vp,
+                               ctypes.c_longlong, vp, vp, vp, vp, sz, vp]),
+    "btc_world_transform": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp]),
+}
+
+AUGMENT_EXPORTED_SYMBOLS = tuple(_AUGMENT_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -207,7 +217,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
