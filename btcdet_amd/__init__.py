@@ -5,12 +5,13 @@ Voxelizer, occupancy/occlusion target generator, sparse-3D-conv rulebook + fused
 
 * ``btcdet_amd.spconv``         -- drop-in for the ``spconv`` v1.2.1 surface BtcDet uses
 * ``btcdet_amd.processor``      -- ``DataProcessor`` voxelization steps on the GPU
-* ``btcdet_amd.device_augmentor`` -- ``DataAugmentor`` (host protocol) and ``DeviceAugmentor``: paste, flip, scale, rotate on a resident batch
+* ``btcdet_amd.device_augmentor`` -- ``DataAugmentor`` (host protocol) and ``DeviceAugmentor``: paste, flip, scale, rotate on a resident batch;
+  ``TemplateBank``: best-match templates resident, ``bm_points`` placed in one launch
 * ``btcdet_amd.occ_targets``    -- ``OccTargets3D`` (occupancy / occlusion grid generator)
 * ``btcdet_amd.vfe`` / ``backbones_3d`` / ``occ_head`` / ``pass_occ_vox`` / ``height_compression``
 
 All compute goes through ``libbtcdet_hip.so`` (hand-written HIP, C ABI in ``include/btcdet_hip.h``, ``btcdet_hip_infer.h``,
-``btcdet_hip_augment.h``).
+``btcdet_hip_augment.h``, ``btcdet_hip_bestmatch.h``).
 """
 __version__ = "0.1.0"
 

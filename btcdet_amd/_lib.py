@@ -1,4 +1,5 @@
-"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h and include/btcdet_hip_augment.h).
+"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h and
+include/btcdet_hip_bestmatch.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -207,6 +208,13 @@ _AUGMENT_SIGS = {
 
 AUGMENT_EXPORTED_SYMBOLS = tuple(_AUGMENT_SIGS.keys())
 
+# the entry point of the fourth public header, include/btcdet_hip_bestmatch.h (same library, same rules)
+_BESTMATCH_SIGS = {
+    "btc_place_templates": (ci, [vp, ctypes.c_longlong, vp, vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_longlong, ci, vp, vp]),
+}
+
+BESTMATCH_EXPORTED_SYMBOLS = tuple(_BESTMATCH_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -217,7 +225,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

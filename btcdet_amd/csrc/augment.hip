@@ -18,26 +18,13 @@
 // All of it is a stream: a KITTI-shaped batch (2 x ~28 k rows of 16 bytes) is bound by its launches (mark, scan, offsets, emit:
 // 18.5 us in all, tools/augment_bench.py), a Waymo-shaped batch (2 x ~160 k rows) by HBM: 16 B read by aug_mark, 1 + 16 B read and 16 or 32 B written by aug_emit per row.  No atomics, no memset, no ticket: every
 // workspace word a kernel reads was written by an earlier launch of the same call.
-#include "btc_common.h"
-
-#include "../../include/btcdet_hip_augment.h"
+#include "aug_ops.h"   // aug_owner, aug_rotate, aug_run_ops: shared with best_match.hip
 
 namespace {
 
 constexpr int AUG_T = 256;
 constexpr int AUG_BOX_CHUNK = 64;
 constexpr int AUG_SMALL_SET = 45;   // rotate_points_along_z: sets below 45 rows (9 n < 400) take the rounded chain
-
-// largest s in [0, count) with offs[s] <= i (offs ascending, offs[0] <= i): the set that owns row i, empty sets skipped
-__device__ __forceinline__ int aug_owner(const int32_t* __restrict__ offs, int count, int i) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (offs[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ bool aug_in_box(float x, float y, float z, const float* __restrict__ b) {
   const float sx = __fsub_rn(x, b[0]), sy = __fsub_rn(y, b[1]);
@@ -137,44 +124,6 @@ __global__ __launch_bounds__(64) void aug_offsets(const unsigned char* __restric
     paste_off[s] = pasted;
     out_offsets[s] = kept + pasted;
   }
-}
-
-// data_side.rotate_points_along_z: p . [[c, s, 0], [-s, c, 0], [0, 0, 1]] with its two roundings
-__device__ __forceinline__ void aug_rotate(float& x, float& y, float& z, float c, float s, bool small_set) {
-  const float r0[3] = {c, s, 0.f}, r1[3] = {-s, c, 0.f}, r2[3] = {0.f, 0.f, 1.f};
-  float o[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    if (small_set) o[j] = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(x, r0[j])), __fmul_rn(y, r1[j])), __fmul_rn(z, r2[j]));
-    else o[j] = __fmaf_rn(z, r2[j], __fmaf_rn(y, r1[j], __fmul_rn(x, r0[j])));
-  }
-  x = o[0], y = o[1], z = o[2];
-}
-
-// runs set `s`'s op program on (x, y, z); (px, py, pz) = the point as it stood at the first ROT (the final point without one).
-// USE_FLAG: the rotation form comes from the op's flag (sets of host-known size) instead of `small_set`
-template <bool USE_FLAG>
-__device__ __forceinline__ void aug_run_ops(const float* __restrict__ ops, const int32_t* __restrict__ op_offsets, int s, bool small_set,
-                                            float& x, float& y, float& z, float& px, float& py, float& pz) {
-  bool snapped = false;
-  if (ops != nullptr) {
-    const int o0 = op_offsets[s];
-    const int cnt = min(max(op_offsets[s + 1] - o0, 0), BTC_AUG_MAX_OPS);
-    for (int k = 0; k < cnt; ++k) {
-      const float* op = ops + (size_t)(o0 + k) * 4;
-      const int kind = (int)op[0];
-      if (kind == BTC_AUG_FLIP_X) {
-        y = -y;
-      } else if (kind == BTC_AUG_SCALE) {
-        const float a = op[1];
-        x = __fmul_rn(x, a), y = __fmul_rn(y, a), z = __fmul_rn(z, a);
-      } else if (kind == BTC_AUG_ROT) {
-        if (!snapped) px = x, py = y, pz = z, snapped = true;
-        aug_rotate(x, y, z, op[1], op[2], USE_FLAG ? (op[3] != 0.f) : small_set);
-      }
-    }
-  }
-  if (!snapped) px = x, py = y, pz = z;
 }
 
 template <bool VEC4>

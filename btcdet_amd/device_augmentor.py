@@ -7,6 +7,10 @@ scans that already lives in HBM (csrc/augment.hip, include/btcdet_hip_augment.h)
                     with the reference's bookkeeping.  Per-scene numpy: what a DataLoader worker runs, and what the device path is
                     compared with (tests/test_augment_cpu.py pins it to the reference's own class, tests/golden/augment.npz).
   ObjectBank        every database object's .bin loaded once into one (sum n_i, F) array, `path -> (first_row, n_rows)`.
+  TemplateBank      every best-match template's .pkl loaded once into one (sum n_i, 3) array, `(class, image_idx, gt_idx) ->
+                    (first_row, n_rows)`: with one, plan() turns the add_multi_best_match step into placements (template rows, yaw
+                    rotation, box centre) and apply() forms `bm_points` in one launch from the resident bank
+                    (csrc/best_match.hip, include/btcdet_hip_bestmatch.h) -- no file is opened and no point formed on the host.
   DeviceAugmentor   plan(scenes): host only, O(boxes) -- runs the augmentor's queue on the boxes of every scene of the batch with the
                     same sampler object, consuming the global numpy RNG exactly as DataAugmentor.forward would for these scenes
                     back to back, and records what the points need: removal boxes, pasted objects, the op program.  It reads no
@@ -18,6 +22,7 @@ scene's shuffle permutation (data_processor.py:41-51) between them: the stream i
 its whole __getitem__ stream.  Permutations are handed to DataProcessor.mask_and_shuffle_batch(shuffle_idx=...) afterwards."""
 import pathlib
 import pickle
+import re
 
 import numpy as np
 import torch
@@ -218,9 +223,68 @@ class ObjectBank(object):
         return self._device[key]
 
 
+class TemplateBank(object):
+    """every best-match template under `template_root` (class name -> directory of <image_idx>_<gt_idx>.pkl) in one array: rows
+    (sum n_i, 3) float32 as data_side.read_bm_template gives them, table (class name, image_idx, gt_idx) -> (first_row, n_rows).
+    keys: an iterable of such triples restricts loading to them (a missing one raises KeyError).  Read once; nothing is known about the
+    size of a real bank, so `nbytes` is there to be looked at before tensor() uploads it."""
+    _NAME = re.compile(r"^(\d+)_(\d+)\.pkl$")
+
+    def __init__(self, template_root, load_point_features=3, keys=None):
+        self.load_point_features = int(load_point_features)
+        found = {}
+        for name in sorted(template_root):
+            directory = pathlib.Path(template_root[name])
+            for path in sorted(directory.iterdir()) if directory.is_dir() else ():
+                m = self._NAME.match(path.name)
+                if m:
+                    found[(str(name), int(m.group(1)), int(m.group(2)))] = path
+        if keys is not None:
+            wanted = [(str(n), int(i), int(g)) for n, i, g in keys]
+            for k in wanted:
+                if k not in found:
+                    raise KeyError("best-match template %s" % (pathlib.Path(template_root[k[0]]) / "{}_{}.pkl".format(k[1], k[2])))
+            found = {k: found[k] for k in sorted(set(wanted))}
+        self._fill({k: data_side.read_bm_template(path, self.load_point_features) for k, path in found.items()})
+
+    @classmethod
+    def from_arrays(cls, arrays, load_point_features=3):
+        """arrays: (class name, image_idx, gt_idx) -> (n, 3) float32 rows; reads no file (tests, synthetic data)"""
+        self = cls.__new__(cls)
+        self.load_point_features = int(load_point_features)
+        self._fill({(str(n), int(i), int(g)): np.asarray(a, dtype=np.float32).reshape(-1, 3) for (n, i, g), a in arrays.items()})
+        return self
+
+    def _fill(self, arrays):
+        self.table, parts, first = {}, [], 0
+        for k in sorted(arrays):
+            self.table[k] = (first, arrays[k].shape[0])
+            parts.append(arrays[k])
+            first += arrays[k].shape[0]
+        assert first < 2 ** 31, "template rows are addressed with int32"
+        self.rows = np.ascontiguousarray(np.concatenate(parts, axis=0), dtype=np.float32) if parts else np.zeros((0, 3), np.float32)
+        self._device = {}
+
+    @property
+    def nbytes(self):
+        return int(self.rows.nbytes)
+
+    def tensor(self, device):
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.rows).to(device).contiguous()
+        return self._device[key]
+
+
 class AugPlan(object):
     """what DeviceAugmentor.plan leaves for apply: flat numpy arrays in the layout of btc_augment_batch, and the host keys per scene"""
     ARRAYS = ("rm_boxes", "rm_offsets", "obj_first", "obj_rows", "obj_shift", "obj_offsets", "ops", "op_offsets", "rot_z")
+    # the layout of btc_place_templates (include/btcdet_hip_bestmatch.h): one placement per box the best-match step serves, in the
+    # host step's order -- bm_first / bm_rows (P) i32 the template's rows in the TemplateBank, bm_place (P, 8) f32 c, ms, s, cx, cy, cz,
+    # 0, 0, bm_offsets (B+1) i32 placements per scene, bm_row_offsets (P+1) i32 the prefix of bm_rows; bm_rows_total its last entry.
+    # bm_device[b]: scene b's bm_points come from placements (its ops rows then carry the small-set flag of ITS bm_points in column
+    # 3, which btc_augment_batch ignores); otherwise from special[b]["bm_points"], made on the host
+    BM_ARRAYS = ("bm_first", "bm_rows", "bm_place", "bm_offsets", "bm_row_offsets")
 
     def __init__(self, batch):
         self.batch = batch
@@ -230,9 +294,12 @@ class AugPlan(object):
 
 
 class DeviceAugmentor(object):
-    def __init__(self, augmentor, bank):
-        self.augmentor, self.bank = augmentor, bank
+    def __init__(self, augmentor, bank, templates=None):
+        self.augmentor, self.bank, self.templates = augmentor, bank, templates
         names = augmentor.queue_names
+        for step in augmentor.data_augmentor_queue:
+            if templates is not None and isinstance(step, MltBestMatchQuerier):
+                assert step.load_point_features == templates.load_point_features, "the bank was read with another LOAD_POINT_FEATURES"
         if "gt_sampling" in names and any(n in WORLD_STEPS for n in names[:names.index("gt_sampling")]):
             raise NotImplementedError("gt_sampling behind a world transform: the kernels remove and paste first")
         if sum(n == "gt_sampling" for n in names) > 1:
@@ -272,17 +339,43 @@ class DeviceAugmentor(object):
             return data_dict
         return paste
 
+    def _plan_best_match(self, step, d, placements):
+        """stands in for MltBestMatchQuerier.__call__ while the plan runs: one placement per box the step would have served, in its
+        order (the scene's own boxes of an in-scope class, then the pasted ones), no file opened, no point formed -> rows placed"""
+        n_aug = d["aug_boxes_image_idx"].shape[0] if "aug_boxes_image_idx" in d else 0
+        boxes, names = d["gt_boxes"], d["gt_names"]
+        n_own = boxes.shape[0] - n_aug
+        assert n_own == d["gt_boxes_inds"].shape[0]
+        image_idx = int(d["frame_id"])
+        served = [(i, image_idx, d["gt_boxes_inds"][i]) for i in range(n_own) if names[i] in step.class_names]
+        if n_aug and "pre_aug_bm" not in d:
+            served += [(n_own + k, d["aug_boxes_image_idx"][k], d["aug_boxes_gt_idx"][k]) for k in range(n_aug)]
+        total = 0
+        for i, img, gt in served:
+            name = names[i]
+            hit = self.templates.table.get((str(name), int(img), int(gt)))
+            if hit is None:
+                raise KeyError("best-match template %s is not in the TemplateBank" % (step.template_root[name] / "{}_{}.pkl".format(img, gt)))
+            yaw = boxes[i][6]                                  # a float32 scalar: the expressions of data_side.get_yaw_rotation
+            c, s = np.cos(yaw), np.sin(yaw)
+            ms = -1.0 * s
+            assert c.dtype == ms.dtype == np.float32
+            placements.append((hit[0], hit[1], (c, ms, s, boxes[i][0], boxes[i][1], boxes[i][2], 0.0, 0.0)))
+            total += hit[1]
+        return total
+
     def plan(self, scenes):
         """scenes: list of dicts with gt_boxes, gt_names, gt_boxes_mask [, road_plane, calib, frame_id, ...]; a `points` key is ignored"""
         aug = self.augmentor
         plan = AugPlan(len(scenes))
         plan.save_pre_rot = self.save_pre_rot
         rm, rm_off, objs, obj_off, ops, op_off, rot_z = [], [0], [], [0], [], [0], []
+        placements, bm_off, plan.bm_device = [], [0], []
         for scene in scenes:
             d = {k: v for k, v in scene.items() if k not in ("points", "pre_rot_points") and k not in SPECIAL_NAMES}
             d["gt_boxes_inds"] = np.arange(list(d["gt_boxes_mask"].shape)[0])
             rec = {"objects": [], "rm_boxes": np.zeros((0, 8), np.float32)}
-            scene_ops, host_special = [], {}
+            scene_ops, host_special, bm_placed = [], {}, None
             for name, step in zip(aug.queue_names, aug.data_augmentor_queue):
                 # a probe point stands in for the scan: the step draws what it draws, transforms the boxes, and shows what it did
                 if name == "gt_sampling":
@@ -292,7 +385,11 @@ class DeviceAugmentor(object):
                         d = step(d)
                     finally:
                         del step._paste
+                elif name == "add_multi_best_match" and self.templates is not None and d["gt_boxes"].dtype == np.float32:
+                    bm_placed = self._plan_best_match(step, d, placements)
                 elif name == "add_multi_best_match":
+                    # without a bank -- or with boxes that are not float32, where the host chain works in float64 and has no single
+                    # device form -- the step runs on the host and the set is uploaded
                     d = step(d)
                     host_special["bm_points"] = np.ascontiguousarray(d.pop("bm_points"), dtype=np.float32)
                 elif name == "random_world_flip":
@@ -321,6 +418,10 @@ class DeviceAugmentor(object):
             rm_off.append(rm_off[-1] + rec["rm_boxes"].shape[0])
             objs.extend(rec["objects"])
             obj_off.append(len(objs))
+            plan.bm_device.append(bm_placed is not None)
+            bm_off.append(len(placements))
+            if bm_placed is not None:      # the rotation form of the scene's bm_points, known here: the kernel takes it from the op
+                scene_ops = [op[:3] + (1.0 if bm_placed < SMALL_SET else 0.0,) for op in scene_ops]
             ops.extend(scene_ops)
             op_off.append(len(ops))
         o = np.array(objs, dtype=np.float64).reshape(-1, 6)
@@ -333,6 +434,14 @@ class DeviceAugmentor(object):
         plan.op_offsets = np.array(op_off, np.int32)
         plan.rot_z = np.array(rot_z, np.float32)
         plan.paste_rows = int(plan.obj_rows.sum())
+        plan.bm_first = np.array([p[0] for p in placements], np.int32)
+        plan.bm_rows = np.array([p[1] for p in placements], np.int32)
+        plan.bm_place = np.array([p[2] for p in placements], np.float32).reshape(-1, 8)
+        plan.bm_offsets = np.array(bm_off, np.int32)
+        row_off = np.concatenate([[0], np.cumsum(plan.bm_rows, dtype=np.int64)])
+        assert row_off[-1] < 2 ** 31, "bm_points rows of a batch are addressed with int32"
+        plan.bm_row_offsets = row_off.astype(np.int32)
+        plan.bm_rows_total = int(plan.bm_row_offsets[-1])
         return plan
 
     # ---------------------------------------------------------------------------------------------------------------- device
@@ -355,13 +464,16 @@ class DeviceAugmentor(object):
             out.append(t[:a.size].view(a.shape) if a.size else t[:0].view(a.shape))
         return out
 
-    def apply(self, points, scene_offsets, plan, special=None, sync=True):
+    def apply(self, points, scene_offsets, plan, special=None, sync=True, indexed_bm=False):
         """points (sum N, F) f32 raw scans on the GPU, scenes contiguous; scene_offsets (B+1) i32; special: name -> (stacked (sum n, 3) f32
         device tensor, offsets (B+1) host ints) of sets in data_side.SPECIAL_NAMES: they get the scene's flip, scale and rotation.
         -> dict: points, pre_rot_points (iff SAVE_PRE_ROT), scene_offsets (device i32), rot_z (device f32 degrees, iff SAVE_PRE_ROT),
         special (name -> (tensor, offsets)), and the plan's host keys as lists over the scenes (gt_boxes, gt_names, ...).
         sync=True trims the point outputs after one (B+1)-int read-back and adds scene_counts; sync=False reads nothing back: the
-        point outputs keep their capacity (N + pasted rows) and scene_offsets[B] on the device says how many rows are valid."""
+        point outputs keep their capacity (N + pasted rows) and scene_offsets[B] on the device says how many rows are valid.
+        A plan made with a TemplateBank: special["bm_points"] is formed from the bank by btc_place_templates (its offsets are known on
+        the host: no read-back either way); indexed_bm=True adds `bm_points`, the (n, 4) [scene, x, y, z] form collate gives the
+        key, from the same launch -- special["bm_points"][0] is then the (n, 3) view of its last three columns."""
         from ._lib import check, lib, ptr, stream_ptr, workspace
         L, dev = lib(), points.device
         B = plan.batch
@@ -371,8 +483,9 @@ class DeviceAugmentor(object):
         assert ld == self.bank.num_point_features or plan.paste_rows == 0, "scan rows and database rows differ in width"
         offs = scene_offsets if (scene_offsets.is_cuda and scene_offsets.dtype == torch.int32) else \
             scene_offsets.to(torch.int32).pin_memory().to(dev, non_blocking=True)
-        (rm_boxes, rm_offsets, obj_first, obj_rows, obj_shift, obj_offsets, ops, op_offsets, rot_z) = self._upload(
-            [getattr(plan, k) for k in AugPlan.ARRAYS], dev)
+        bm_device = any(getattr(plan, "bm_device", ()))
+        up = self._upload([getattr(plan, k) for k in AugPlan.ARRAYS + (AugPlan.BM_ARRAYS if bm_device else ())], dev)
+        (rm_boxes, rm_offsets, obj_first, obj_rows, obj_shift, obj_offsets, ops, op_offsets, rot_z) = up[:len(AugPlan.ARRAYS)]
         bank = self.bank.tensor(dev)
         cap = n + plan.paste_rows
         out = torch.empty((cap, ld), dtype=torch.float32, device=dev)
@@ -410,6 +523,22 @@ class DeviceAugmentor(object):
             check(L.btc_world_transform(ptr(t) if t.shape[0] else None, t.shape[0], t.shape[1], ptr(d_so), B, ptr(d_ops) if sp_ops.size else None,
                                         ptr(op_offsets), ptr(o) if t.shape[0] else None, stream_ptr()), "btc_world_transform")
             res["special"][name] = (o, so)
+        if bm_device:
+            assert special is None or "bm_points" not in special, "bm_points comes from the plan's placements and from the caller"
+            placed, placed_offs = self._place_templates(plan, up[len(AugPlan.ARRAYS):], ops, op_offsets, 4 if indexed_bm else 3, dev)
+            if "bm_points" in res["special"]:      # some scenes took the host route: per scene, in scene order
+                hosted, hosted_offs = res["special"]["bm_points"]
+                if indexed_bm:
+                    col = torch.repeat_interleave(torch.arange(B, dtype=torch.float32), torch.from_numpy(np.diff(hosted_offs).astype(np.int64)))
+                    hosted = torch.cat([col.to(dev, non_blocking=True)[:, None], hosted], dim=1)
+                parts = [(placed[placed_offs[b]:placed_offs[b + 1]] if plan.bm_device[b] else hosted[hosted_offs[b]:hosted_offs[b + 1]]) for b in range(B)]
+                placed = torch.cat(parts, dim=0)
+                placed_offs = np.cumsum([0] + [p.shape[0] for p in parts]).astype(np.int32)
+            if indexed_bm:
+                res["bm_points"] = placed
+            res["special"]["bm_points"] = (placed[:, 1:] if indexed_bm else placed, placed_offs)
+        elif indexed_bm:
+            raise ValueError("indexed_bm=True needs a plan whose bm_points come from a TemplateBank")
         for k in sorted({k for s in plan.scenes for k in s}):
             res[k] = [s.get(k) for s in plan.scenes]
         if plan.save_pre_rot:
@@ -423,6 +552,20 @@ class DeviceAugmentor(object):
         if out_pre is not None:
             res["pre_rot_points"] = out_pre
         return res
+
+
+    def _place_templates(self, plan, bm_arrays, ops, op_offsets, out_ld, dev):
+        """btc_place_templates over the plan's placements -> ((bm_rows_total, out_ld) tensor, (B+1) host offsets of the scenes' rows)"""
+        from ._lib import check, lib, ptr, stream_ptr
+        bm_first, bm_rows, bm_place, bm_offsets, bm_row_offsets = bm_arrays
+        bank = self.templates.tensor(dev)
+        n_pl, n_out = int(plan.bm_first.shape[0]), plan.bm_rows_total
+        out = torch.empty((n_out, out_ld), dtype=torch.float32, device=dev)
+        check(lib().btc_place_templates(ptr(bank) if n_pl else None, bank.shape[0], ptr(bm_first) if n_pl else None, ptr(bm_rows) if n_pl else None,
+                                        ptr(bm_place) if n_pl else None, ptr(bm_offsets), ptr(bm_row_offsets), n_pl, plan.batch,
+                                        ptr(ops) if plan.ops.size else None, ptr(op_offsets), n_out, out_ld, ptr(out) if n_out else None, stream_ptr()),
+              "btc_place_templates")
+        return out, plan.bm_row_offsets[plan.bm_offsets]
 
 
 _TORCH_DTYPE = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "uint8": torch.uint8}
