@@ -1,5 +1,5 @@
-"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h and
-include/btcdet_hip_bestmatch.h).
+"""ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
+include/btcdet_hip_bestmatch.h and include/btcdet_hip_frames.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -215,6 +215,14 @@ _BESTMATCH_SIGS = {
 
 BESTMATCH_EXPORTED_SYMBOLS = tuple(_BESTMATCH_SIGS.keys())
 
+# the entry points of the fifth public header, include/btcdet_hip_frames.h (same library, same rules)
+_FRAMES_SIGS = {
+    "btc_fov_crop_ws_bytes": (sz, [ci, ci]),
+    "btc_fov_crop": (ci, [vp, ci, ci, vp, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
+}
+
+FRAMES_EXPORTED_SYMBOLS = tuple(_FRAMES_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -225,7 +233,8 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
+                                  list(_FRAMES_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
