@@ -1,20 +1,9 @@
-// The per-row pieces the augmentation kernels share (augment.hip, best_match.hip): the owner search over an ascending offsets array,
-// the z rotation with its two roundings, and the op program of include/btcdet_hip_augment.h.
+// The per-row pieces the augmentation kernels share (augment.hip, best_match.hip): the z rotation with its two roundings and the op
+// program of include/btcdet_hip_augment.h; the owner search over an ascending offsets array comes with compact.h.
 #pragma once
-#include "btc_common.h"
+#include "compact.h"
 
 #include "../../include/btcdet_hip_augment.h"
-
-// largest s in [0, count) with offs[s] <= i (offs ascending, offs[0] <= i): the set that owns row i, empty sets skipped
-static __device__ __forceinline__ int aug_owner(const int32_t* __restrict__ offs, int count, int i) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (offs[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 // data_side.rotate_points_along_z: p . [[c, s, 0], [-s, c, 0], [0, 0, 1]] with its two roundings
 static __device__ __forceinline__ void aug_rotate(float& x, float& y, float& z, float c, float s, bool small_set) {

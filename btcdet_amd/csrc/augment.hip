@@ -10,19 +10,19 @@
 //   (scan)       btc_scan_exclusive_i32 over the workgroup counts (csrc/scan.hip).
 //   aug_offsets  one wave per scene boundary: kept rows and pasted rows in front of it -> out_offsets; one more wave ranks the
 //                objects' row counts (exclusive prefix) for aug_emit's row -> object search.
-//   aug_emit     workgroups [0, nb): the kept scan rows, stable rank = ballot + popcount within the wave, wave counts within the
-//                workgroup, the workgroup's prefix; workgroups [nb, ..): one thread per pasted row, bank[first + i] shifted in double.
+//   aug_emit     workgroups [0, nb): the kept scan rows at their stable rank (compact.h); workgroups [nb, ..): one thread per pasted
+//                row, bank[first + i] shifted in double.
 //                Every emitted row runs its scene's op program and is stored to `out`, and to `out_pre` as it stood at the first ROT.
 //   aug_world    the op program alone over stacked sets.
 //
 // All of it is a stream: a KITTI-shaped batch (2 x ~28 k rows of 16 bytes) is bound by its launches (mark, scan, offsets, emit:
 // 18.5 us in all, tools/augment_bench.py), a Waymo-shaped batch (2 x ~160 k rows) by HBM: 16 B read by aug_mark, 1 + 16 B read and 16 or 32 B written by aug_emit per row.  No atomics, no memset, no ticket: every
 // workspace word a kernel reads was written by an earlier launch of the same call.
-#include "aug_ops.h"   // aug_owner, aug_rotate, aug_run_ops: shared with best_match.hip
+#include "aug_ops.h"   // aug_rotate, aug_run_ops: shared with best_match.hip; compact.h: the compaction's stages, aug_owner
 
 namespace {
 
-constexpr int AUG_T = 256;
+constexpr int AUG_T = BTC_COMPACT_T;
 constexpr int AUG_BOX_CHUNK = 64;
 constexpr int AUG_SMALL_SET = 45;   // rotate_points_along_z: sets below 45 rows (9 n < 400) take the rounded chain
 
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(AUG_T) void aug_mark(const float* __restrict__ pts,
   }
   bool removed = false;
   if (row0 < n && rm_boxes != nullptr) {
-    const int last = min(row0 + AUG_T, n) - 1;
-    const int s_lo = aug_owner(scene_offsets, batch, row0), s_hi = aug_owner(scene_offsets, batch, last);   // uniform in the workgroup
+    int s_lo, s_hi;
+    btc_compact_scene_span(scene_offsets, batch, row0, n, s_lo, s_hi);
     for (int s = s_lo; s <= s_hi; ++s) {
       const int b0 = rm_offsets[s], b1 = rm_offsets[s + 1];
       for (int c0 = b0; c0 < b1; c0 += AUG_BOX_CHUNK) {
@@ -70,10 +70,9 @@ __global__ __launch_bounds__(AUG_T) void aug_mark(const float* __restrict__ pts,
       }
     }
   }
-  const int keep = live && !removed;
+  const bool keep = live && !removed;
   if (live) keep_flag[i] = (unsigned char)keep;
-  const int c = __syncthreads_count(keep);
-  if (threadIdx.x == 0) block_cnt[blockIdx.x] = c;
+  btc_compact_count(keep, block_cnt);
 }
 
 // blocks [0, batch]: boundary s -> kept_off[s] = kept scan rows in front of scene s, paste_off[s] = pasted rows in front of it,
@@ -101,17 +100,7 @@ __global__ __launch_bounds__(64) void aug_offsets(const unsigned char* __restric
     return;
   }
   const int s = blockIdx.x;
-  const int pos = s == batch ? n : min(max(scene_offsets[s], 0), n);
-  int kept;
-  if (pos >= n) {
-    kept = *total;
-  } else {
-    const int blk = pos / AUG_T;
-    int cnt = 0;
-    for (int j = blk * AUG_T + lane; j < pos; j += 64) cnt += keep_flag[j];
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-    kept = block_prefix[blk] + __shfl(cnt, 0);
-  }
+  const int kept = btc_compact_boundary(s, scene_offsets, batch, n, block_prefix, total, [=](int j) -> int { return keep_flag[j]; });
   int pasted = 0;
   if (n_objects > 0) {
     const int j1 = min(max(obj_offsets[s], 0), n_objects);
@@ -145,7 +134,6 @@ __global__ __launch_bounds__(AUG_T) void aug_emit(const float* __restrict__ pts,
                                                   const int32_t* __restrict__ paste_off, const float* __restrict__ ops,
                                                   const int32_t* __restrict__ op_offsets, const int32_t* __restrict__ out_offsets,
                                                   long long out_capacity, float* __restrict__ out, float* __restrict__ out_pre) {
-  __shared__ int s_wave[AUG_T / 64];
   float x, y, z;
   float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
   const float* rest = nullptr;   // columns 3.. of the source row (scalar path)
@@ -154,13 +142,8 @@ __global__ __launch_bounds__(AUG_T) void aug_emit(const float* __restrict__ pts,
   if ((int)blockIdx.x < nb) {
     const int i = blockIdx.x * AUG_T + threadIdx.x;
     const bool keep = (i < n) && keep_flag[i] != 0;
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
+    const int rank = btc_compact_rank(keep, block_prefix);
     if (!keep) return;
-    int rank = block_prefix[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += s_wave[w];
     s = aug_owner(scene_offsets, batch, i);
     dst = (long long)rank + paste_off[s];
     const float* p = pts + (size_t)i * ld;
@@ -238,17 +221,12 @@ __global__ __launch_bounds__(AUG_T) void aug_world(const float* __restrict__ in,
   else aug_store_row<false>(o, ld, x, y, z, p + 3);
 }
 
-bool aug_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int aug_blocks(int n_rows) { return btc_cdiv(n_rows > 0 ? n_rows : 1, AUG_T); }
-
 }  // namespace
 
 extern "C" size_t btc_augment_ws_bytes(int n_rows, int batch, int n_objects) {
   if (n_rows < 0 || batch < 1 || n_objects < 0) return 0;
-  const long long nb = aug_blocks(n_rows);
-  return btc_align((size_t)(n_rows > 0 ? n_rows : 1)) + btc_align((size_t)(nb + 1) * sizeof(int32_t)) * 2 + 256 +
-         btc_align((size_t)(batch + 1) * sizeof(int32_t)) * 2 + btc_align((size_t)(n_objects + 1) * sizeof(int32_t)) + btc_scan_ws_bytes(nb);
+  return BtcCompactWs::bytes(n_rows, true) + btc_align((size_t)(batch + 1) * sizeof(int32_t)) * 2 +
+         btc_align((size_t)(n_objects + 1) * sizeof(int32_t));   // kept_off, paste_off, obj_prefix
 }
 
 extern "C" int btc_augment_batch(const float* points, int n_rows, int ld, const int32_t* scene_offsets, int batch, const float* rm_boxes,
@@ -272,33 +250,28 @@ extern "C" int btc_augment_batch(const float* points, int n_rows, int ld, const 
   BTC_CHECK_ARG(n_objects == 0 || (bank && obj_first && obj_rows && obj_shift && obj_offsets), "btc_augment_batch: missing pointer (bank or obj_*)");
   BTC_CHECK_ARG(out || out_capacity == 0, "btc_augment_batch: missing pointer (out)");
   BTC_CHECK_ARG(ws_bytes >= btc_augment_ws_bytes(n_rows, batch, n_objects), "btc_augment_batch: workspace too small");
-  const int nb = aug_blocks(n_rows);
-  BtcCarver c(ws);
-  unsigned char* keep_flag = c.take<unsigned char>(n_rows > 0 ? n_rows : 1);
-  int32_t* block_cnt = c.take<int32_t>(nb + 1);
-  int32_t* block_prefix = c.take<int32_t>(nb + 1);
-  int32_t* total = c.take<int32_t>(1);
-  int32_t* kept_off = c.take<int32_t>(batch + 1);
-  int32_t* paste_off = c.take<int32_t>(batch + 1);
-  int32_t* obj_prefix = c.take<int32_t>(n_objects + 1);
-  void* scan_ws = c.base + c.off;
-  aug_mark<<<nb, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, rm_boxes, rm_offsets, keep_flag, block_cnt);
+  BtcCompactWs w(ws, n_rows, true);
+  int32_t* kept_off = w.c.take<int32_t>(batch + 1);
+  int32_t* paste_off = w.c.take<int32_t>(batch + 1);
+  int32_t* obj_prefix = w.c.take<int32_t>(n_objects + 1);
+  const int nb = w.nb;
+  aug_mark<<<nb, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, rm_boxes, rm_offsets, w.keep_flag, w.block_cnt);
   BTC_LAUNCH_CHECK();
-  int rc = btc_scan_exclusive_i32(block_cnt, block_prefix, nb, total, scan_ws, stream);
+  int rc = w.scan(stream);
   if (rc != BTC_OK) return rc;
-  aug_offsets<<<batch + 2, 64, 0, stream>>>(keep_flag, n_rows, scene_offsets, batch, block_prefix, total, obj_rows, obj_offsets, n_objects, kept_off,
-                                           paste_off, obj_prefix, out_offsets);
+  aug_offsets<<<batch + 2, 64, 0, stream>>>(w.keep_flag, n_rows, scene_offsets, batch, w.block_prefix, w.total, obj_rows, obj_offsets, n_objects,
+                                           kept_off, paste_off, obj_prefix, out_offsets);
   BTC_LAUNCH_CHECK();
   const int grid = (n_rows > 0 ? nb : 0) + btc_cdiv(paste_rows, AUG_T);
   if (grid > 0) {
     const int nb_scan = n_rows > 0 ? nb : 0;
-    const bool vec = ld == 4 && aug_aligned16(points) && aug_aligned16(bank) && aug_aligned16(out) && aug_aligned16(out_pre);
+    const bool vec = ld == 4 && btc_aligned16(points) && btc_aligned16(bank) && btc_aligned16(out) && btc_aligned16(out_pre);
     if (vec)
-      aug_emit<true><<<grid, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, keep_flag, block_prefix, nb_scan, bank, bank_rows, obj_first,
+      aug_emit<true><<<grid, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, w.keep_flag, w.block_prefix, nb_scan, bank, bank_rows, obj_first,
                                                  obj_shift, obj_offsets, n_objects, paste_rows, obj_prefix, kept_off, paste_off, ops, op_offsets,
                                                  out_offsets, out_capacity, out, out_pre);
     else
-      aug_emit<false><<<grid, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, keep_flag, block_prefix, nb_scan, bank, bank_rows, obj_first,
+      aug_emit<false><<<grid, AUG_T, 0, stream>>>(points, n_rows, ld, scene_offsets, batch, w.keep_flag, w.block_prefix, nb_scan, bank, bank_rows, obj_first,
                                                   obj_shift, obj_offsets, n_objects, paste_rows, obj_prefix, kept_off, paste_off, ops, op_offsets,
                                                   out_offsets, out_capacity, out, out_pre);
     BTC_LAUNCH_CHECK();
@@ -317,7 +290,7 @@ extern "C" int btc_world_transform(const float* in, int n_rows, int ld, const in
   BTC_CHECK_ARG(in != out || n_rows == 0, "btc_world_transform: out may not alias in");
   if (n_rows == 0) return BTC_OK;
   const int nb = btc_cdiv(n_rows, AUG_T);
-  if (ld == 4 && aug_aligned16(in) && aug_aligned16(out)) aug_world<true><<<nb, AUG_T, 0, stream>>>(in, n_rows, ld, set_offsets, batch, ops, op_offsets, out);
+  if (ld == 4 && btc_aligned16(in) && btc_aligned16(out)) aug_world<true><<<nb, AUG_T, 0, stream>>>(in, n_rows, ld, set_offsets, batch, ops, op_offsets, out);
   else aug_world<false><<<nb, AUG_T, 0, stream>>>(in, n_rows, ld, set_offsets, batch, ops, op_offsets, out);
   BTC_LAUNCH_CHECK();
   return BTC_OK;

@@ -6,19 +6,19 @@
 //                header's formulas are the contract, and a fused form moves a point that sits within an ulp of an image edge across it).
 //                -> keep flag per row, kept count per workgroup.
 //   (scan)       btc_scan_exclusive_i32 over the workgroup counts (csrc/scan.hip).
-//   fov_scatter  the kept rows, stable rank = ballot + popcount within the wave, wave counts within the workgroup, the workgroup's
-//                prefix.  It reads the flag fov_mark wrote, so the count and the scatter cannot disagree.
+//   fov_scatter  the kept rows at their stable rank (compact.h).  It reads the flag fov_mark wrote, so the count and the scatter
+//                cannot disagree.
 //   fov_offsets  one wave per scene boundary: kept rows in front of it, from the same flags.
 //
 // A stream: 16 B read by fov_mark, 1 + 16 B read and at most 16 + 4 B written by fov_scatter per row of a (n, 4) scan.  No atomics, no
 // memset, no ticket: every workspace word a kernel reads was written by an earlier launch of the same call.
-#include "aug_ops.h"   // aug_owner
+#include "compact.h"   // the compaction's count, rank, boundary, row copy and workspace; aug_owner
 
 #include "../../include/btcdet_hip_frames.h"
 
 namespace {
 
-constexpr int FOV_T = 256;
+constexpr int FOV_T = BTC_COMPACT_T;
 constexpr int FOV_CAL = BTC_FOV_CALIB_FLOATS;
 constexpr int FOV_CHUNK = FOV_T / FOV_CAL;   // calibration blocks staged per pass: one float per thread
 
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(FOV_T) void fov_mark(const float* __restrict__ pts,
   }
   bool keep = false;
   if (row0 < n) {
-    const int last = min(row0 + FOV_T, n) - 1;
-    const int s_lo = aug_owner(scene_offsets, batch, row0), s_hi = aug_owner(scene_offsets, batch, last);   // uniform in the workgroup
+    int s_lo, s_hi;
+    btc_compact_scene_span(scene_offsets, batch, row0, n, s_lo, s_hi);
     for (int c0 = s_lo; c0 <= s_hi; c0 += FOV_CHUNK) {
       const int s = c0 + (int)threadIdx.x / FOV_CAL;
       __syncthreads();   // the previous chunk has been read
@@ -71,32 +71,18 @@ __global__ __launch_bounds__(FOV_T) void fov_mark(const float* __restrict__ pts,
     }
   }
   if (live) keep_flag[i] = (unsigned char)keep;
-  const int c = __syncthreads_count(keep);
-  if (threadIdx.x == 0) block_cnt[blockIdx.x] = c;
+  btc_compact_count(keep, block_cnt);
 }
 
 template <bool VEC4>
 __global__ __launch_bounds__(FOV_T) void fov_scatter(const float* __restrict__ pts, int n, int ld, const unsigned char* __restrict__ keep_flag,
                                                      const int32_t* __restrict__ block_prefix, int out_capacity, float* __restrict__ out,
                                                      int32_t* __restrict__ keep_idx) {
-  __shared__ int s_wave[FOV_T / 64];
   const int i = blockIdx.x * FOV_T + threadIdx.x;
   const bool keep = (i < n) && keep_flag[i] != 0;
-  const unsigned long long m = __ballot(keep);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  if (!keep) return;
-  int dst = block_prefix[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) dst += s_wave[w];
-  if (dst < 0 || dst >= out_capacity) return;
-  const float* p = pts + (size_t)i * ld;
-  float* o = out + (size_t)dst * ld;
-  if (VEC4) {
-    *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(p);
-  } else {
-    for (int c = 0; c < ld; ++c) o[c] = p[c];
-  }
+  const int dst = btc_compact_rank(keep, block_prefix);
+  if (!keep || dst < 0 || dst >= out_capacity) return;
+  btc_copy_row<VEC4>(pts + (size_t)i * ld, out + (size_t)dst * ld, ld);
   if (keep_idx) keep_idx[dst] = i;
 }
 
@@ -104,31 +90,15 @@ __global__ __launch_bounds__(FOV_T) void fov_scatter(const float* __restrict__ p
 __global__ __launch_bounds__(64) void fov_offsets(const unsigned char* __restrict__ keep_flag, int n, const int32_t* __restrict__ scene_offsets,
                                                   int batch, const int32_t* __restrict__ block_prefix, const int32_t* __restrict__ total,
                                                   int32_t* __restrict__ out_offsets) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const int pos = s == batch ? n : min(max(scene_offsets[s], 0), n);
-  int kept;
-  if (pos >= n) {
-    kept = *total;
-  } else {
-    const int blk = pos / FOV_T;
-    int cnt = 0;
-    for (int j = blk * FOV_T + lane; j < pos; j += 64) cnt += keep_flag[j];
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-    kept = block_prefix[blk] + __shfl(cnt, 0);
-  }
-  if (lane == 0) out_offsets[s] = kept;
+  const int kept = btc_compact_boundary(blockIdx.x, scene_offsets, batch, n, block_prefix, total, [=](int j) -> int { return keep_flag[j]; });
+  if (threadIdx.x == 0) out_offsets[blockIdx.x] = kept;
 }
-
-bool fov_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int fov_blocks(int n) { return btc_cdiv(n > 0 ? n : 1, FOV_T); }
 
 }  // namespace
 
 extern "C" size_t btc_fov_crop_ws_bytes(int n, int batch) {
   if (n < 0 || batch < 1) return 0;
-  const long long nb = fov_blocks(n);
-  return btc_align((size_t)(n > 0 ? n : 1)) + btc_align((size_t)(nb + 1) * sizeof(int32_t)) * 2 + 256 + btc_scan_ws_bytes(nb);
+  return BtcCompactWs::bytes(n, true);
 }
 
 extern "C" int btc_fov_crop(const float* points, int n, int ld, const int32_t* scene_offsets, int batch, const float* calib, int out_capacity,
@@ -141,25 +111,19 @@ extern "C" int btc_fov_crop(const float* points, int n, int ld, const int32_t* s
   BTC_CHECK_ARG(scene_offsets && calib && out_offsets && ws, "btc_fov_crop: missing pointer (scene_offsets, calib, out_offsets or ws)");
   BTC_CHECK_ARG((points && out) || n == 0, "btc_fov_crop: missing pointer (points or out)");
   BTC_CHECK_ARG(ws_bytes >= btc_fov_crop_ws_bytes(n, batch), "btc_fov_crop: workspace too small");
-  const int nb = fov_blocks(n);
-  BtcCarver c(ws);
-  unsigned char* keep_flag = c.take<unsigned char>(n > 0 ? n : 1);
-  int32_t* block_cnt = c.take<int32_t>(nb + 1);
-  int32_t* block_prefix = c.take<int32_t>(nb + 1);
-  int32_t* total = c.take<int32_t>(1);
-  void* scan_ws = c.base + c.off;
-  const bool vec = ld == 4 && fov_aligned16(points) && fov_aligned16(out);
-  if (vec) fov_mark<true><<<nb, FOV_T, 0, stream>>>(points, n, ld, scene_offsets, batch, calib, keep_flag, block_cnt);
-  else fov_mark<false><<<nb, FOV_T, 0, stream>>>(points, n, ld, scene_offsets, batch, calib, keep_flag, block_cnt);
+  const BtcCompactWs w(ws, n, true);
+  const bool vec = ld == 4 && btc_aligned16(points) && btc_aligned16(out);
+  if (vec) fov_mark<true><<<w.nb, FOV_T, 0, stream>>>(points, n, ld, scene_offsets, batch, calib, w.keep_flag, w.block_cnt);
+  else fov_mark<false><<<w.nb, FOV_T, 0, stream>>>(points, n, ld, scene_offsets, batch, calib, w.keep_flag, w.block_cnt);
   BTC_LAUNCH_CHECK();
-  int rc = btc_scan_exclusive_i32(block_cnt, block_prefix, nb, total, scan_ws, stream);
+  int rc = w.scan(stream);
   if (rc != BTC_OK) return rc;
   if (n > 0) {
-    if (vec) fov_scatter<true><<<nb, FOV_T, 0, stream>>>(points, n, ld, keep_flag, block_prefix, out_capacity, out, keep_idx);
-    else fov_scatter<false><<<nb, FOV_T, 0, stream>>>(points, n, ld, keep_flag, block_prefix, out_capacity, out, keep_idx);
+    if (vec) fov_scatter<true><<<w.nb, FOV_T, 0, stream>>>(points, n, ld, w.keep_flag, w.block_prefix, out_capacity, out, keep_idx);
+    else fov_scatter<false><<<w.nb, FOV_T, 0, stream>>>(points, n, ld, w.keep_flag, w.block_prefix, out_capacity, out, keep_idx);
     BTC_LAUNCH_CHECK();
   }
-  fov_offsets<<<batch + 1, 64, 0, stream>>>(keep_flag, n, scene_offsets, batch, block_prefix, total, out_offsets);
+  fov_offsets<<<batch + 1, 64, 0, stream>>>(w.keep_flag, n, scene_offsets, batch, w.block_prefix, w.total, out_offsets);
   BTC_LAUNCH_CHECK();
   return BTC_OK;
 }

@@ -126,6 +126,10 @@ int btc_voxel_shift_col(float* voxels, const int32_t* coords, int m, int max_poi
  *   h_range_xyxy  host float[4] = x_lo, y_lo, x_hi, y_hi
  *   out (n, ld), out_b (n, ld_b): rows [0, n') valid ; out_offsets (batch+1) i32: scene offsets after masking,
  *   out_offsets[batch] = n' ; keep_idx (n) i32 or NULL: source row of every kept row.  ws: btc_range_mask_ws_bytes(n).
+ *   A scene offset outside [0, n] is read as the nearer end; out_offsets[batch] is n' whatever scene_offsets[batch] holds.
+ *   Refused with BTC_EINVAL before anything is enqueued: n < 0, ld < 2, batch < 1; a missing pointer (scene_offsets, h_range_xyxy,
+ *   out_offsets or ws; points or out unless n == 0); points_b without out_b or with ld_b < 1; a workspace below
+ *   btc_range_mask_ws_bytes(n); an empty range (x_lo > x_hi or y_lo > y_hi).
  *
  * btc_gather_rows: out[i] = src[idx[i]] (DataProcessor.shuffle_points, data_processor.py:41-51: points[shuffle_idx]).
  *   an index outside [0, n_src) writes a zero row and increments *bad_count (if given) instead of reading out of bounds. */

@@ -72,3 +72,33 @@ def test_exempt_entry_points_take_no_stream():
 def test_every_case_has_a_gpu_test():
     fns = _gpu_case_functions()
     assert set(CASES) == fns, "cases without a test: %s; tests without a case: %s" % (sorted(set(CASES) - fns), sorted(fns - set(CASES)))
+
+
+P = 0x1000      # a non-null address nobody reads: every call below returns from its argument checks
+
+
+def test_range_mask_argument_checks_return_before_any_launch():
+    import ctypes
+    import numpy as np
+    from btcdet_amd import _lib
+    L = _lib.lib()
+    lim = np.array([0.0, -40.0, 70.4, 40.0], np.float32)
+
+    def call(pts=P, pts_b=P, n=300, ld=4, ld_b=4, offs=P, batch=2, rng=lim, out=P, out_b=P, out_offs=P, keep_idx=None, ws=P, ws_bytes=1 << 20):
+        h = rng if rng is None else _lib.f32p(np.ascontiguousarray(rng, dtype=np.float32))
+        return L.btc_range_mask_compact(pts, pts_b, n, ld, ld_b, offs, batch, h, out, out_b, out_offs, keep_idx, ws, ws_bytes, None)
+    for kw in ("offs", "rng", "out_offs", "ws"):
+        assert call(**{kw: None}) == -1 and b"missing pointer (scene_offsets, h_range_xyxy, out_offsets or ws)" in L.btc_last_error(), kw
+    for kw in ("pts", "out"):
+        assert call(**{kw: None}) == -1 and b"missing pointer (points or out)" in L.btc_last_error(), kw
+    assert call(out_b=None) == -1 and b"second array needs its output and row length" in L.btc_last_error()
+    assert call(ld_b=0) == -1 and b"second array needs its output and row length" in L.btc_last_error()
+    # the refusals from before the pointer checks keep their messages
+    for kw in ({"ld": 1}, {"ld": 0}, {"batch": 0}, {"batch": -1}, {"n": -1}):
+        assert call(**kw) == -1 and b"need n >= 0, ld >= 2 (x, y columns), batch >= 1" in L.btc_last_error(), kw
+    need = L.btc_range_mask_ws_bytes(300)
+    for ws_bytes in (0, 8, need - 1):
+        assert call(ws_bytes=ws_bytes) == -1 and b"workspace too small" in L.btc_last_error(), ws_bytes
+    for rng in ([1.0, 0.0, 0.5, 2.0], [0.0, 3.0, 1.0, 2.0]):
+        assert call(rng=rng) == -1 and b"empty range" in L.btc_last_error(), rng
+    assert ctypes.sizeof(ctypes.c_float) * 4 == lim.nbytes
