@@ -87,20 +87,7 @@ int btc_apply(const char* who, int pass, int operands, const void* src, long lon
 // conv_apply_bf16.hip: bf16 operands on the bf16 matrix pipe; Wq[k][Cres][Cred] bf16
 int btc_apply_bf16w(const void* src, const void* Wq, const float* bias, const int32_t* nbr, const int32_t* order, int n_rows, int K, int Cred,
                     int Cres, void* dst, hipStream_t stream, int mirror = 0, const struct BnFuse* bn = nullptr);
-// the weight gradient's families outside conv_wgrad.hip, which holds the planner that chooses among them (and the fp32-pipe families)
-// conv_wgrad_x.hip: weight gradient on the bf16 matrix pipe (mode 0: bf16 activations, 1: fp32 activations as three exact bf16 pieces);
-// cg / cc = channels of the gathered / contiguous operand of the row walk
-bool btc_wgrad_x_supported(int mode, int K, int cg, int cc);
-int btc_wgrad_x_plan(int mode, int rows, int K, int cg, int cc, int* S, int* ph, int* z = nullptr);   // -> offset groups; *S = slabs, *z = channel blocks
-int btc_launch_wgrad_x(int mode, const void* g, const void* c, const int32_t* map, const int32_t* ord, int rows, int K, int cg, int cc, float* part,
-                       int swap, hipStream_t stream);
-// conv_wgrad_n.hip: weight gradient of a layer with a narrow result side (<= 8 channels), walked over the layer's INPUT rows: x read once,
-// dy gathered through the backward map (mirror: a submanifold layer's forward map, column k' = offset K-1-k'); fp32 matrix pipe
-// ... or with a narrow input (<= 8 channels: the first layers), walked over its OUTPUT rows with the features gathered through nbr_out
-int btc_wgrad_n_kind(int K, int Cin, int Cout);   // 1 narrow result, 2 narrow input, 0 neither
-int btc_wgrad_n_plan(int rows);   // -> slabs
-int btc_launch_wgrad_n(bool bf, const void* walked, const void* gathered, const int32_t* map, int rows, int K, int Cw, int Cn, float* part,
-                       int flags /* 1 mirrored map, 2 narrow input (slab written [k][narrow][walked]) */, hipStream_t stream);
+// (the weight gradient's families -- conv_wgrad.hip, conv_wgrad_x.hip, conv_wgrad_n.hip -- share conv_wgrad.h: the launch record and the plans)
 constexpr size_t BTC_SCRATCH_HEAD = 64 * 1024;              // head of a registered scratch buffer: zeroed at registration, zero between launches
 constexpr long long BTC_SCRATCH_TICKETS = BTC_SCRATCH_HEAD / 4;   // (the z-split launches' per-tile tickets live there)
 void* btc_scratch(hipStream_t stream, size_t* bytes);   // the stream's registered scratch buffer (btc_set_scratch) or NULL

@@ -3,8 +3,9 @@
 // weight-gradient call -- the families of conv_wgrad_x.hip (bf16 matrix pipe) and conv_wgrad_n.hip (narrow layers) included.
 //
 // Every family writes S partial sums ("slabs") of K * Cin * Cout floats into the caller's workspace; wgrad_reduce adds them up in slab
-// order (deterministic).  btc_conv_wgrad_ws_bytes is computed from the same per-family plans the launch uses (wgrad_max_slabs).
-#include "btc_common.h"
+// order (deterministic).  A family's plan function fills the launch record of conv_wgrad.h (instance, grid, LDS bytes, S) or refuses the
+// shape; btc_conv_wgrad_ws_bytes asks the same plan functions (wgrad_max_slabs), and the launch is the record's: L.fn(L, a).
+#include "conv_wgrad.h"
 
 namespace {
 
@@ -605,15 +606,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
     }
 }
 
-// dW[e] = sum_s part[s][e] in slab order (deterministic); 8 loads in flight per thread
-__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ part, int S, long long count,
-                                                    float* __restrict__ dW) {
-  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= count) return;
+// sum_s part[s][e] in slab order (deterministic): a chain of S dependent additions per element, bound by the round trips of its loads --
+// 16 in flight, then 8, then single terms; the order of the additions is the slab order either way
+__device__ __forceinline__ float wgrad_slab_sum(const float* __restrict__ part, int S, long long count, long long e) {
   float s = 0.f;
   int q = 0;
-  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
-  // additions is the slab order either way)
   for (; q + 16 <= S; q += 16) {
     float v[16];
 #pragma unroll
@@ -629,7 +626,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ pa
     for (int u = 0; u < 8; ++u) s += v[u];
   }
   for (; q < S; ++q) s += part[(size_t)q * count + e];
-  dW[e] = s;
+  return s;
+}
+
+// dW[e] = sum_s part[s][e]
+__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ part, int S, long long count,
+                                                    float* __restrict__ dW) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  dW[e] = wgrad_slab_sum(part, S, count, e);
 }
 
 // the slab reductions of MANY layers in one launch (btc_wgrad_reduce_multi: every weight gradient of a backward pass whose dW nobody
@@ -649,68 +654,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi(const ReduceJobs jobs)
   const long long e = (long long)((int)blockIdx.x - jobs.block0[j]) * 256 + threadIdx.x;
   const long long count = jobs.count[j];
   if (e >= count) return;
-  const float* __restrict__ part = jobs.part[j];
-  const int S = jobs.S[j];
-  float s = 0.f;
-  int q = 0;
-  // (a chain of S dependent additions per element, bound by the round trips of its loads: 16 in flight, then 8; the order of the
-  // additions is the slab order either way)
-  for (; q + 16 <= S; q += 16) {
-    float v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) s += v[u];
-  }
-  for (; q + 8 <= S; q += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(q + u) * count + e];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; q < S; ++q) s += part[(size_t)q * count + e];
-  jobs.dW[j][e] = s;
+  jobs.dW[j][e] = wgrad_slab_sum(jobs.part[j], jobs.S[j], count, e);
 }
 
 // ---- host side: one planner (wgrad_choose) decides everything about a call; btc_conv_wgrad_ws_bytes asks the same per-family plans ----
-
-// what the caller has
-struct WgradCall {
-  int n_out, K, Cin, Cout;
-  int n_in;      // rows of the backward map, < 0: there is none (a submanifold layer's mirrored forward map counts as none: the kernels
-                 // that walk the output rows take nothing from it)
-  int n_feat;    // rows of `feat`, < 0: unknown
-  bool mirror;   // nbr_in == nbr_out: the backward map is the forward map with the offset index mirrored (rulebook.hip)
-};
-
-// One side of the rulebook as a row walk: the walked operand's rows are read once, in order, the other operand's rows are gathered
-// through the map.  swap = 0: the OUTPUT rows (walked dout, gathered feat, nbr_out, order_out); swap = 1: the INPUT rows (walked feat,
-// gathered dout, nbr_in or the mirrored nbr_out, order_in) and the slab is written transposed, so dW keeps its [K][Cin][Cout] layout.
-struct WgradWalk {
-  int swap, rows;
-  int Cg, Cc;    // channels of the gathered / the walked (contiguous) operand
-};
-
-struct WgradArgs {   // the operands of the chosen walk
-  const float *g, *c;
-  const int32_t *map, *ord;
-  int K;
-  float* part;
-  hipStream_t stream;
-};
-
-enum WgradFamily { WG_N, WG_X, WG_ROWS_P, WG_ROWS, WG_PARTIAL_P, WG_PARTIAL };
-
-struct WgradLaunch {
-  WgradFamily family;
-  int S;                                                 // slabs the launch writes
-  WgradWalk walk;
-  void (*fn)(const WgradLaunch&, const WgradArgs&);      // fp32-pipe families: the template instance
-  size_t lds;                                            // ... and its dynamic LDS bytes
-  int groups;                                            // rows_p / rows: offset groups
-  int n_cblk, n_mblk, tiles_per_split;                   // partial_p / partial
-};
 
 template <int MT, int NT, int KB, int PH, bool BF>
 void launch_wgrad_rows_p(const WgradLaunch& L, const WgradArgs& a) {
@@ -730,7 +677,7 @@ void launch_wgrad_rows(const WgradLaunch& L, const WgradArgs& a) {
 
 template <int NT, bool BF, bool PIPE>
 void launch_wgrad_partial(const WgradLaunch& L, const WgradArgs& a) {
-  const dim3 grid(a.K, L.S, L.n_mblk * L.n_cblk);
+  const dim3 grid(a.K, L.S, L.blocks);
   const WgradWalk& w = L.walk;   // (the output rows: Cg = Cin, Cc = Cout)
   if (PIPE) conv_wgrad_partial_p<NT, BF><<<grid, 256, L.lds, a.stream>>>(a.g, a.c, a.map, w.rows, a.K, w.Cg, w.Cc, L.tiles_per_split, L.n_cblk, a.part);
   else conv_wgrad_partial<NT, BF><<<grid, 256, L.lds, a.stream>>>(a.g, a.c, a.map, w.rows, a.K, w.Cg, w.Cc, L.tiles_per_split, L.n_cblk, a.part);
@@ -739,24 +686,28 @@ void launch_wgrad_partial(const WgradLaunch& L, const WgradArgs& a) {
 // ---- the instance tables (each macro spells the template instances of one table row, nothing else) ----
 // rows_p / rows: (MT, NT) 16-wide tiles of the gathered / walked channels -> KB offsets per LDS phase, PH phases per offset group
 struct RowsTile {
-  int mt, nt, kb, ph;
-  void (*fn[2][4])(const WgradLaunch&, const WgradArgs&);   // [bf16 activations][PH variant]
+  int mt, nt, kb;
+  int n_auto;      // the work split picks among ph[0 .. n_auto); a variant after those is reached through BTC_TUNE_WGRAD_PH only
+  int ph[4];       // the PH of each variant, 0: none
+  WgradFn fn[2][4];   // [bf16 activations][PH variant]
 };
 // conv_wgrad_rows_p: variants PH = ph, ph / 2 (its own (KB, PH) per tile shape: the B fragments live in registers, LDS holds the
 // double-buffered gather tile only)
-#define ROWS_P_TILE(MT, NT, KB, PH)                                                                                        \
-  {MT, NT, KB, PH, {{launch_wgrad_rows_p<MT, NT, KB, PH, false>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, false>},         \
-                    {launch_wgrad_rows_p<MT, NT, KB, PH, true>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, true>}}}
+#define ROWS_P_TILE(MT, NT, KB, PH)                                                                                                  \
+  {MT, NT, KB, 2, {PH, PH / 2}, {{launch_wgrad_rows_p<MT, NT, KB, PH, false>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, false>},      \
+                                 {launch_wgrad_rows_p<MT, NT, KB, PH, true>, launch_wgrad_rows_p<MT, NT, KB, PH / 2, true>}}}
 const RowsTile ROWS_P_TILES[] = {ROWS_P_TILE(1, 1, 4, 4), ROWS_P_TILE(2, 1, 2, 8), ROWS_P_TILE(1, 2, 4, 4), ROWS_P_TILE(2, 2, 2, 8),
                                  ROWS_P_TILE(3, 2, 2, 4), ROWS_P_TILE(2, 4, 2, 4), ROWS_P_TILE(4, 2, 1, 8), ROWS_P_TILE(4, 4, 1, 4)};
 #undef ROWS_P_TILE
-// conv_wgrad_rows: variants PH = 1, 2, 4, 7 and ph = 0 (the work split picks one), or the one PH named
-#define ROWS_TILE(MT, NT, KB)                                                                                                                          \
-  {MT, NT, KB, 0, {{launch_wgrad_rows<MT, NT, KB, 1, false>, launch_wgrad_rows<MT, NT, KB, 2, false>, launch_wgrad_rows<MT, NT, KB, 4, false>,        \
-                    launch_wgrad_rows<MT, NT, KB, 7, false>},                                                                                         \
-                   {launch_wgrad_rows<MT, NT, KB, 1, true>, launch_wgrad_rows<MT, NT, KB, 2, true>, launch_wgrad_rows<MT, NT, KB, 4, true>,           \
-                    launch_wgrad_rows<MT, NT, KB, 7, true>}}}
-const RowsTile ROWS_TILES[] = {{1, 1, 8, 4, {{nullptr, nullptr, launch_wgrad_rows<1, 1, 8, 4, false>}, {nullptr, nullptr, launch_wgrad_rows<1, 1, 8, 4, true>}}},
+// conv_wgrad_rows: variants PH = 4, 2, 1 for the work split and PH = 7 (it no longer fits two workgroups per CU) for the key; the
+// 16 -> 16 shape has the one PH named
+#define ROWS_TILE(MT, NT, KB)                                                                                                                \
+  {MT, NT, KB, 3, {4, 2, 1, 7},                                                                                                              \
+   {{launch_wgrad_rows<MT, NT, KB, 4, false>, launch_wgrad_rows<MT, NT, KB, 2, false>, launch_wgrad_rows<MT, NT, KB, 1, false>,             \
+     launch_wgrad_rows<MT, NT, KB, 7, false>},                                                                                              \
+    {launch_wgrad_rows<MT, NT, KB, 4, true>, launch_wgrad_rows<MT, NT, KB, 2, true>, launch_wgrad_rows<MT, NT, KB, 1, true>,                \
+     launch_wgrad_rows<MT, NT, KB, 7, true>}}}
+const RowsTile ROWS_TILES[] = {{1, 1, 8, 1, {4}, {{launch_wgrad_rows<1, 1, 8, 4, false>}, {launch_wgrad_rows<1, 1, 8, 4, true>}}},
                                ROWS_TILE(2, 1, 4), ROWS_TILE(1, 2, 4), ROWS_TILE(2, 2, 4), ROWS_TILE(3, 2, 2), ROWS_TILE(2, 4, 2), ROWS_TILE(4, 2, 2),
                                ROWS_TILE(4, 4, 1)};
 #undef ROWS_TILE
@@ -765,8 +716,7 @@ static_assert(sizeof(ROWS_P_TILES) == sizeof(ROWS_TILES), "the two row-stationar
 // partial_p / partial: NT = 1, 2, 4, 8 16-column tiles of Cout per workgroup
 #define PARTIAL_NT(BF, PIPE) \
   {launch_wgrad_partial<1, BF, PIPE>, launch_wgrad_partial<2, BF, PIPE>, launch_wgrad_partial<4, BF, PIPE>, launch_wgrad_partial<8, BF, PIPE>}
-void (*const PARTIAL_FN[2][2][4])(const WgradLaunch&, const WgradArgs&) = {{PARTIAL_NT(false, false), PARTIAL_NT(false, true)},
-                                                                          {PARTIAL_NT(true, false), PARTIAL_NT(true, true)}};   // [bf16][pipe][log2 NT]
+const WgradFn PARTIAL_FN[2][2][4] = {{PARTIAL_NT(false, false), PARTIAL_NT(false, true)}, {PARTIAL_NT(true, false), PARTIAL_NT(true, true)}};   // [bf16][pipe][log2 NT]
 #undef PARTIAL_NT
 
 // ---- the walks ----
@@ -781,7 +731,7 @@ WgradWalk wgrad_short_walk(const WgradCall& c) {
 // an operand of `rows` rows x C elements of esz bytes that a kernel reaches through 32-bit byte offsets (4 GB)
 bool wgrad_fits32(long long rows, long long C, long long esz) { return rows * C * esz < 0xFFFFFF00LL; }
 
-// ---- per-family plans: false = the family does not take this shape; true = *L describes its launch ----
+// ---- per-family plans (conv_wgrad.h): false = the family does not take this shape; true = *L describes its launch ----
 
 // row-stationary kernels: supported (MT, NT) tile shapes and enough rows to amortise the persistent walk
 bool wgrad_plan_rows(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
@@ -790,42 +740,24 @@ bool wgrad_plan_rows(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunc
   for (int i = 0; i < N_ROWS_TILES; ++i)
     if (ROWS_TILES[i].mt == mt && ROWS_TILES[i].nt == nt) tile = i;
   if (tile < 0 || w.rows < 4096 || c.K > 64) return false;
-  // Work split (tools/conv_bench.py, MI355X): two workgroups per CU (512 in all) = row splits x offset groups.  More
-  // phases per group = fewer groups re-reading the dOut tile but a larger accumulator slab per workgroup (PH = 7 no
-  // longer fits two workgroups per CU) and more slab traffic; the largest PH <= 4 that still leaves >= 3 row tiles
-  // per workgroup measured best from 12 K to 210 K rows (e.g. 32->32 at 210 K rows 307 -> 219 us, at 12 K rows 63 -> 30 us).
-  const int t_ph = btc_tune_get(BTC_TUNE_WGRAD_PH), t_wgs = btc_tune_get(BTC_TUNE_WGRAD_WGS);
   // software-pipelined variant (conv_wgrad_rows_p) when the gathered operand's channel count is a multiple of 4
   const bool pipe = (w.Cg & (bf ? 7 : 3)) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1;   // bf16: 8-channel gathers
-  const int wgs = t_wgs ? t_wgs : 512;
-  const int n_tiles = btc_cdiv(w.rows, TM);
   const RowsTile& t = pipe ? ROWS_P_TILES[tile] : ROWS_TILES[tile];
-  int ph = t.ph;
-  if (pipe) {
-    // few tiles: half the phases per workgroup = twice the offset groups = twice the workgroups
-    if ((long long)n_tiles * btc_cdiv(c.K, t.kb * ph) < 3LL * wgs) ph >>= 1;
-    if (t_ph == ph * 2 || t_ph * 2 == ph) ph = t_ph;   // tuning runs: the other variant
-    L->fn = t.fn[bf][ph == t.ph ? 0 : 1];
-    // As[2][KB][TM][LDA] | s_nbr[3][TM][KB * PH] | s_row[3][TM]
-    L->lds = (size_t)(2 * t.kb * TM * ldb_of(mt)) * sizeof(float) + (size_t)(3 * TM * t.kb * ph + 3 * TM) * sizeof(int32_t);
-  } else {
-    if (!ph) {
-      ph = 1;
-      for (int cand = 4; cand > 1; cand >>= 1)
-        if ((long long)n_tiles * btc_cdiv(c.K, t.kb * cand) >= 3LL * wgs) { ph = cand; break; }
-      if (t_ph) ph = t_ph;
-    }
-    L->fn = t.fn[bf][ph == 1 ? 0 : (ph == 2 ? 1 : (ph == 4 ? 2 : 3))];
-    // As[KB][TM][LDA] | Ds[TM][LDB] | s_nbr[TM][K] | s_kact[K] | s_row[TM]
-    L->lds = (size_t)(t.kb * TM * ldb_of(mt) + TM * ldb_of(nt)) * sizeof(float) + (size_t)(TM * c.K + c.K + TM) * sizeof(int32_t);
-  }
+  // the PH variants the work split chooses from -- or, in tuning runs, the one variant of this tile row that BTC_TUNE_WGRAD_PH names
+  const int t_ph = btc_tune_get(BTC_TUNE_WGRAD_PH);
+  int v0 = 0, n_ph = t.n_auto;
+  for (int i = 0; i < 4; ++i)
+    if (t_ph && t.ph[i] == t_ph) v0 = i, n_ph = 1;
+  const WgradSplit s = wgrad_split(btc_cdiv(w.rows, TM), c.K, t.kb, t.ph + v0, n_ph, 1);
+  *L = WgradLaunch{};
   L->family = pipe ? WG_ROWS_P : WG_ROWS;
+  L->S = s.S;
   L->walk = w;
-  L->groups = btc_cdiv(c.K, t.kb * ph);
-  int S = wgs / L->groups;
-  if (S > n_tiles / 2) S = n_tiles / 2;  // at least two row tiles per persistent workgroup
-  if (S > n_tiles) S = n_tiles;
-  L->S = S < 1 ? 1 : S;
+  L->fn = t.fn[bf][v0 + s.i];
+  // rows_p: As[2][KB][TM][LDA] | s_nbr[3][TM][KB * PH] | s_row[3][TM];  rows: As[KB][TM][LDA] | Ds[TM][LDB] | s_nbr[TM][K] | s_kact[K] | s_row[TM]
+  L->lds = pipe ? (size_t)(2 * t.kb * TM * ldb_of(mt)) * sizeof(float) + (size_t)(3 * TM * t.kb * s.ph + 3 * TM) * sizeof(int32_t)
+                : (size_t)(t.kb * TM * ldb_of(mt) + TM * ldb_of(nt)) * sizeof(float) + (size_t)(TM * c.K + c.K + TM) * sizeof(int32_t);
+  L->groups = s.groups;
   return true;
 }
 
@@ -833,42 +765,20 @@ bool wgrad_plan_rows(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunc
 void wgrad_plan_partial(bool bf, const WgradCall& c, WgradLaunch* L) {
   const bool pipe = ((c.Cin | c.Cout) & 3) == 0 && btc_tune_get(BTC_TUNE_WGRAD_PIPE) != 1;
   const int lnt = c.Cout <= 16 ? 0 : (c.Cout <= 32 ? 1 : (c.Cout <= 64 ? 2 : 3)), nt = 1 << lnt;
+  *L = WgradLaunch{};
   L->family = pipe ? WG_PARTIAL_P : WG_PARTIAL;
   L->walk = wgrad_walk(c, 0, c.n_out);
   L->fn = PARTIAL_FN[bf][pipe][lnt];
   L->lds = (size_t)(TM * WG_LDA + TM * ldb_of(nt)) * sizeof(float) + (4 * TM + 2) * sizeof(int32_t);
   L->n_cblk = btc_cdiv(c.Cout, nt * 16);
-  L->n_mblk = btc_cdiv(c.Cin, 64);
+  L->blocks = btc_cdiv(c.Cin, 64) * L->n_cblk;
   const int n_tiles = btc_cdiv(c.n_out > 0 ? c.n_out : 1, TM);
-  int S = 1536 / (c.K * L->n_cblk * L->n_mblk);
+  int S = 1536 / (c.K * L->blocks);
   if (S > 32) S = 32;
   if (S < 1) S = 1;
   if (S > n_tiles) S = n_tiles;
   L->tiles_per_split = btc_cdiv(n_tiles, S);
   L->S = btc_cdiv(n_tiles, L->tiles_per_split);
-}
-
-// the row-stationary walk on the bf16 matrix pipe (conv_wgrad_x.hip): bf16 activations as they are, fp32 activations as three exact
-// bf16 pieces; any channel counts whose gathered side is a multiple of 16 (a workgroup owns a <= 64 x 64 block of every dW[k])
-bool wgrad_plan_x(bool bf, const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
-  const int mode = bf ? 0 : 1;
-  if (w.rows < 2048 || !btc_wgrad_x_supported(mode, c.K, w.Cg, w.Cc)) return false;
-  int ph;
-  L->family = WG_X;
-  L->walk = w;
-  btc_wgrad_x_plan(mode, w.rows, c.K, w.Cg, w.Cc, &L->S, &ph);
-  return true;
-}
-
-// narrow layers on the fp32 matrix pipe (conv_wgrad_n.hip): kind 1, a narrow RESULT (the 5-channel occupancy head), walks the layer's
-// INPUT rows -- x read once, dy gathered; kind 2, a narrow INPUT (the 4- / 6-channel first layers), walks the OUTPUT rows -- dOut read
-// once, the features gathered through nbr_out
-bool wgrad_plan_n(const WgradCall& c, const WgradWalk& w, WgradLaunch* L) {
-  if (btc_wgrad_n_kind(c.K, c.Cin, c.Cout) != (w.swap ? 1 : 2)) return false;
-  L->family = WG_N;
-  L->walk = w;
-  L->S = btc_wgrad_n_plan(w.rows);
-  return true;
 }
 
 // the most slabs any launch of this call can write: every family that takes the shape, for both activation types and both walk sides --
@@ -882,13 +792,13 @@ int wgrad_max_slabs(const WgradCall& c) {
     // (the bf16 instances of the pipelined kernel want 8-channel gathers, so the two plans can differ)
     if (!wgrad_plan_rows(bf, c, w, &L)) wgrad_plan_partial(bf, c, &L);
     if (L.S > S) S = L.S;
-    if (wgrad_plan_x(bf, c, out, &L) && L.S > S) S = L.S;
-    if (w.swap && wgrad_plan_x(bf, c, w, &L) && L.S > S) S = L.S;
+    if (btc_wgrad_x_plan(bf, c.K, out, &L) && L.S > S) S = L.S;
+    if (w.swap && btc_wgrad_x_plan(bf, c.K, w, &L) && L.S > S) S = L.S;
   }
   // narrow layers: either walk side at either row count (kind 1 walks n_out rows where the map is mirrored)
   for (int swap = 0; swap < 2; ++swap) {
-    if (wgrad_plan_n(c, wgrad_walk(c, swap, c.n_out), &L) && L.S > S) S = L.S;
-    if (c.n_in > 0 && wgrad_plan_n(c, wgrad_walk(c, swap, c.n_in), &L) && L.S > S) S = L.S;
+    if (btc_wgrad_n_plan(c, wgrad_walk(c, swap, c.n_out), false, &L) && L.S > S) S = L.S;
+    if (c.n_in > 0 && btc_wgrad_n_plan(c, wgrad_walk(c, swap, c.n_in), false, &L) && L.S > S) S = L.S;
   }
   return S;
 }
@@ -902,18 +812,18 @@ WgradLaunch wgrad_choose(bool bf, const WgradCall& c) {
   if (btc_tune_get(BTC_TUNE_WGRAD_NARROW) != 1) {
     // (n reaches its map through 32-bit offsets as well)
     const WgradWalk in = wgrad_walk(c, 1, c.mirror ? c.n_out : c.n_in), out = wgrad_walk(c, 0, c.n_out);
-    if ((c.mirror || c.n_in >= 0) && in.rows >= 2048 && fits && wgrad_fits32(in.rows, c.K, 4) && wgrad_plan_n(c, in, &L)) return L;
+    if ((c.mirror || c.n_in >= 0) && in.rows >= 2048 && fits && wgrad_fits32(in.rows, c.K, 4) && btc_wgrad_n_plan(c, in, bf, &L)) return L;
     // (not where the rulebook's input side is less than half the output side: the kernels below walk that side -- 4 -> 16 from 8.4 K to
     // 40 K rows: 13.6 us there, 23.8 here)
-    if (!(c.n_in >= 0 && 2LL * c.n_in < c.n_out) && out.rows >= 2048 && fits && wgrad_fits32(out.rows, c.K, 4) && wgrad_plan_n(c, out, &L)) return L;
+    if (!(c.n_in >= 0 && 2LL * c.n_in < c.n_out) && out.rows >= 2048 && fits && wgrad_fits32(out.rows, c.K, 4) && btc_wgrad_n_plan(c, out, bf, &L)) return L;
   }
   const WgradWalk w = wgrad_short_walk(c);
-  if (btc_tune_get(BTC_TUNE_WGRAD_X) != 1 && (bf || btc_tune_get(BTC_TUNE_SPLIT) != 1) && fits && wgrad_plan_x(bf, c, w, &L)) return L;
+  if (btc_tune_get(BTC_TUNE_WGRAD_X) != 1 && (bf || btc_tune_get(BTC_TUNE_SPLIT) != 1) && fits && btc_wgrad_x_plan(bf, c.K, w, &L)) return L;
   if (!wgrad_plan_rows(bf, c, w, &L)) wgrad_plan_partial(bf, c, &L);
   return L;
 }
 
-// every family ends the same way
+// every family ends the same way: the check of its launch, then the slabs
 int wgrad_finish(const float* part, int S, long long count, float* dW, int* slabs_out, hipStream_t stream) {
   BTC_LAUNCH_CHECK();
   if (slabs_out) {
@@ -954,14 +864,7 @@ int wgrad_impl(bool bf, const void* feat_, const void* dout_, const int32_t* nbr
                 (int)L.family, L.S);
   const int swap = L.walk.swap;
   const WgradArgs a = {swap ? dout : feat, swap ? feat : dout, swap && !c.mirror ? nbr_in : nbr_out, swap ? order_in : order_out, K, (float*)ws, stream};
-  int rc = BTC_OK;
-  if (L.family == WG_N)   // flags: 1 mirrored map, 2 narrow input
-    rc = btc_launch_wgrad_n(bf, a.c, a.g, a.map, L.walk.rows, K, L.walk.Cc, L.walk.Cg, a.part, swap ? (c.mirror ? 1 : 0) : 2, stream);
-  else if (L.family == WG_X)
-    rc = btc_launch_wgrad_x(bf ? 0 : 1, a.g, a.c, a.map, a.ord, L.walk.rows, K, L.walk.Cg, L.walk.Cc, a.part, swap, stream);
-  else
-    L.fn(L, a);
-  if (rc != BTC_OK) return rc;
+  L.fn(L, a);
   return wgrad_finish(a.part, L.S, count, dW, slabs_out, stream);
 }
 

@@ -20,7 +20,7 @@
 // The backward map of a submanifold layer is its forward map with the offset index mirrored (rulebook.hip): `mirror` reads column k' of
 // nbr_out as nbr_in's column K-1-k', i.e. writes dW[K-1-k'].  The four waves of a workgroup add their blocks in wave order through LDS,
 // one slab per workgroup, slabs added in index order by wgrad_reduce / btc_wgrad_reduce_multi: deterministic.
-#include "btc_common.h"
+#include "conv_wgrad.h"
 
 namespace {
 
@@ -165,46 +165,38 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_wgrad_n(const void* __restric
   }
 }
 
-}  // namespace
-
-// a layer with a narrow RESULT (Cout <= 8: walked over its input rows, Cin a multiple of 16) or a narrow INPUT (Cin <= 8: walked over its
-// output rows, Cout a multiple of 16): -> 1 / 2, or 0
-int btc_wgrad_n_kind(int K, int Cin, int Cout) {
-  if (K < 1 || K > 64 || Cin < 1 || Cout < 1) return 0;   // (K <= 64: a dead row's map offsets, N_RECORDS + 4 k', must stay below 2^32)
-  if (Cout <= 8 && K * Cout <= 16 * NTL_MAX && Cin >= 16 && (Cin & 15) == 0) return 1;
-  if (Cin <= 8 && K * Cin <= 16 * NTL_MAX && Cout >= 16 && (Cout & 15) == 0) return 2;
-  return 0;
+// the walked operand is the contiguous one of the walk (a.c, L.walk.Cc channels), the gathered one (a.g) has the <= 8 channels
+template <int MT, int NTL, bool BF>
+void launch_n(const WgradLaunch& L, const WgradArgs& a) {
+  conv_wgrad_n<MT, NTL, BF><<<dim3(L.S, L.blocks), NW * 64, 0, a.stream>>>(a.c, a.g, a.map, L.walk.rows, a.K, L.walk.Cc, L.walk.Cg, a.part, L.flags);
 }
 
-// slabs (= workgroups along x) of a launch over `rows` walked rows
-int btc_wgrad_n_plan(int rows) {
+// the instances: 16 or 32 walked channels per workgroup x 9 or 11 column tiles (K Cn <= 144 / <= 176) x the activation type
+#define N_TILE(MT, NTL) {launch_n<MT, NTL, false>, launch_n<MT, NTL, true>}
+const WgradFn N_FN[2][2][2] = {{N_TILE(1, 9), N_TILE(1, 11)}, {N_TILE(2, 9), N_TILE(2, 11)}};   // [32 channels][wide][bf16]
+#undef N_TILE
+
+}  // namespace
+
+// a narrow RESULT (Cout <= 8, Cin a multiple of 16) is taken over the input rows (w.swap), a narrow INPUT (Cin <= 8, Cout a multiple of 16)
+// over the output rows; K (k', narrow channel) columns in at most 11 tiles
+bool btc_wgrad_n_plan(const WgradCall& c, const WgradWalk& w, bool bf, WgradLaunch* L) {
+  const int Cn = w.Cg, Cw = w.Cc;
+  if (c.K < 1 || c.K > 64 || Cn < 1) return false;   // (K <= 64: a dead row's map offsets, N_RECORDS + 4 k', must stay below 2^32)
+  if (Cn > 8 || c.K * Cn > 16 * NTL_MAX || Cw < 16 || (Cw & 15) != 0) return false;
   const int t_wgs = btc_tune_get(BTC_TUNE_WGRAD_WGS);
   // one workgroup per CU: every slab is 4 K Cin Cout bytes written and read again, and one more term of the reduction's chain
   // (256 / 512 / 768 slabs: 48 / 61 / 77 us at 210 K rows)
   int s = t_wgs ? t_wgs : 256;
-  const int n_groups = btc_cdiv(rows, 4);
+  const int n_groups = btc_cdiv(w.rows, 4);
   if (s > n_groups / (8 * NW)) s = n_groups / (8 * NW);   // at least 8 groups a wave
-  return s < 1 ? 1 : s;
-}
-
-// walked: rows of Cw channels (a multiple of 16), read once; gathered: rows of Cn <= 8 channels through map (rows x K); flags as the kernel's
-int btc_launch_wgrad_n(bool bf, const void* walked, const void* gathered, const int32_t* map, int rows, int K, int Cw, int Cn, float* part, int flags,
-                       hipStream_t stream) {
-  BTC_CHECK_ARG(K >= 1 && K <= 64 && Cn >= 1 && Cn <= 8 && K * Cn <= 16 * NTL_MAX && Cw >= 16 && (Cw & 15) == 0,
-                "btc_launch_wgrad_n: unsupported shape %d x %d, K = %d", Cw, Cn, K);
-  const int S = btc_wgrad_n_plan(rows);
-  const bool wide = K * Cn > 144, two = (Cw & 31) == 0;
-  dim3 grid(S, Cw / (two ? 32 : 16));
-#define N_LAUNCH(MT_, NTL_)                                                                                                            \
-  do {                                                                                                                                 \
-    if (bf) conv_wgrad_n<MT_, NTL_, true><<<grid, NW * 64, 0, stream>>>(walked, gathered, map, rows, K, Cw, Cn, part, flags);          \
-    else conv_wgrad_n<MT_, NTL_, false><<<grid, NW * 64, 0, stream>>>(walked, gathered, map, rows, K, Cw, Cn, part, flags);            \
-  } while (0)
-  if (two && !wide) N_LAUNCH(2, 9);
-  else if (two) N_LAUNCH(2, 11);
-  else if (!wide) N_LAUNCH(1, 9);
-  else N_LAUNCH(1, 11);
-#undef N_LAUNCH
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  const bool wide = c.K * Cn > 144, two = (Cw & 31) == 0;
+  *L = WgradLaunch{};
+  L->family = WG_N;
+  L->S = s < 1 ? 1 : s;
+  L->walk = w;
+  L->fn = N_FN[two][wide][bf];
+  L->blocks = Cw / (two ? 32 : 16);
+  L->flags = w.swap ? (c.mirror ? 1 : 0) : 2;
+  return true;
 }

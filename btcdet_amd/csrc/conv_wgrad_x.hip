@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "conv_tile.h"
+#include "conv_wgrad.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -34,7 +35,7 @@ namespace {
 
 constexpr int TMX = 64;   // rows per tile: two 32-row MFMA steps
 // both operands travel through raw buffer descriptors with 32-bit byte offsets: the host side refuses tensors of 4 GB or more
-// (btc_wgrad_x_supported's callers fall back to conv_wgrad_rows_p), an offset past num_records returns zeros without a fetch
+// (conv_wgrad.hip wgrad_choose: such a call goes to conv_wgrad_rows_p), an offset past num_records returns zeros without a fetch
 #define X_RECORDS 0xFFFFFF00u
 #define X_ABSENT 0xFFFFFFF0u
 
@@ -404,37 +405,46 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
     }
 }
 
-template <int MT, int NT, int KB, int PH, int MODE, int DEPTH>
-size_t lds_x() {
-  constexpr int NPL = MODE ? 3 : 1;
-  constexpr int RING = (DEPTH == 2 && PH == 1) ? 4 : 3;
-  constexpr int RROW = DEPTH == 2 ? RING + 1 : RING;
-  return (size_t)2 * KB * NPL * TMX * (MT * 32 + 16) + (size_t)(RING * TMX * PH * KB + RROW * TMX) * sizeof(int32_t);
+// dynamic LDS bytes of conv_wgrad_x<MT, *, KB, PH, MODE, DEPTH>: As[2][KB][NPL][TMX] rows of RS bytes | s_nbr[RING][TMX][PH KB] | s_row[RROW][TMX]
+size_t lds_x(int mt, int kb, int ph, int mode, int depth) {
+  const int npl = mode ? 3 : 1;
+  const int ring = (depth == 2 && ph == 1) ? 4 : 3;
+  const int rrow = depth == 2 ? ring + 1 : ring;
+  return (size_t)2 * kb * npl * TMX * (mt * 32 + 16) + (size_t)(ring * TMX * ph * kb + rrow * TMX) * sizeof(int32_t);
 }
 
 template <int MT, int NT, int KB, int PH, int MODE, int DEPTH>
-void launch_x(dim3 grid, hipStream_t stream, const void* g, const void* c, const int32_t* map, const int32_t* ord, int rows, int K, int cg_all,
-              int cc_all, float* part, int swap) {
+void launch_x(const WgradLaunch& L, const WgradArgs& a) {
   static BtcPerDeviceOnce once;
   btc_once_per_device(once, [] {
     (void)hipFuncSetAttribute((const void*)conv_wgrad_x<MT, NT, KB, PH, MODE, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
-  conv_wgrad_x<MT, NT, KB, PH, MODE, DEPTH><<<grid, 256, lds_x<MT, NT, KB, PH, MODE, DEPTH>(), stream>>>(g, c, map, ord, rows, K, cg_all, cc_all, part, swap);
+  conv_wgrad_x<MT, NT, KB, PH, MODE, DEPTH><<<dim3(L.S, L.groups, L.blocks), 256, L.lds, a.stream>>>(a.g, a.c, a.map, a.ord, L.walk.rows, a.K, L.walk.Cg,
+                                                                                                   L.walk.Cc, a.part, L.walk.swap);
 }
 
-// (KB, PH) per tile shape; PH is halved when the launch has too few (tile, group, block) triples to fill the machine
-struct XShape {
+// ---- the instance tables, one per mode (the macro spells the template instances of one table row, nothing else) ----
+// (MT, NT) 16-wide tiles of the gathered / contiguous channels -> KB offsets per item, PH phases per offset group; PH is halved when the
+// launch has too few (tile, group, block) triples to fill the machine (wgrad_split)
+struct XTile {
   int mt, nt, kb, ph;
+  WgradFn fn[2][2];   // [PH | PH / 2][DEPTH 1 | 2]
 };
-const XShape X_BF16[] = {{4, 4, 1, 4}, {4, 2, 1, 8}, {2, 4, 2, 4}, {3, 2, 2, 4}, {2, 2, 2, 8}, {2, 1, 2, 8}, {1, 2, 4, 4}, {1, 1, 4, 4}};
-const XShape X_SPLIT[] = {{4, 4, 1, 2}, {4, 2, 1, 4}, {2, 4, 2, 2}, {3, 2, 2, 2}, {2, 2, 2, 4}, {2, 1, 2, 8}, {1, 2, 2, 8}};
+#define X_TILE(MT, NT, KB, PH, MODE)                                                                 \
+  {MT, NT, KB, PH, {{launch_x<MT, NT, KB, PH, MODE, 1>, launch_x<MT, NT, KB, PH, MODE, 2>},          \
+                    {launch_x<MT, NT, KB, PH / 2, MODE, 1>, launch_x<MT, NT, KB, PH / 2, MODE, 2>}}}
+const XTile X_BF16_TILES[] = {X_TILE(4, 4, 1, 4, 0), X_TILE(4, 2, 1, 8, 0), X_TILE(2, 4, 2, 4, 0), X_TILE(3, 2, 2, 4, 0),
+                              X_TILE(2, 2, 2, 8, 0), X_TILE(2, 1, 2, 8, 0), X_TILE(1, 2, 4, 4, 0), X_TILE(1, 1, 4, 4, 0)};
+const XTile X_SPLIT_TILES[] = {X_TILE(4, 4, 1, 2, 1), X_TILE(4, 2, 1, 4, 1), X_TILE(2, 4, 2, 2, 1), X_TILE(3, 2, 2, 2, 1),
+                               X_TILE(2, 2, 2, 4, 1), X_TILE(2, 1, 2, 8, 1), X_TILE(1, 2, 2, 8, 1)};
+#undef X_TILE
 
 // the tile shape of a launch: the gathered operand's channels in whole blocks of 16 MT (48 channels: MT = 3, else the largest of 4, 2, 1
 // that divides), the contiguous operand's in blocks of the smallest 16 NT that covers them (at most 64)
-const XShape* find_shape(int mode, int cg_all, int cc_all) {
+const XTile* find_shape(int mode, int cg_all, int cc_all) {
   if (cg_all <= 0 || cc_all <= 0 || (cg_all & 15)) return nullptr;
-  const XShape* tab = mode ? X_SPLIT : X_BF16;
-  const int n = mode ? (int)(sizeof(X_SPLIT) / sizeof(XShape)) : (int)(sizeof(X_BF16) / sizeof(XShape));
+  const XTile* tab = mode ? X_SPLIT_TILES : X_BF16_TILES;
+  const int n = mode ? (int)(sizeof(X_SPLIT_TILES) / sizeof(XTile)) : (int)(sizeof(X_BF16_TILES) / sizeof(XTile));
   const int nt_want = cc_all <= 16 ? 1 : (cc_all <= 32 ? 2 : 4);
   for (int nt = nt_want; nt >= 1; nt >>= 1)
     for (int i = 0; i < n; ++i) {   // (the tables list the larger gathered blocks first)
@@ -448,71 +458,23 @@ const XShape* find_shape(int mode, int cg_all, int cc_all) {
 
 }  // namespace
 
-// mode: 0 = bf16 activations, 1 = fp32 activations (split operands); cg / cc: channels of the gathered / contiguous operand
-bool btc_wgrad_x_supported(int mode, int K, int cg, int cc) {
-  if (K > 64 || K < 1) return false;
-  return find_shape(mode, cg, cc) != nullptr;
-}
-
-// the work split of a launch: -> offset groups, *S = row splits (slabs), *ph = phases per group actually used, *z = channel blocks
-int btc_wgrad_x_plan(int mode, int rows, int K, int cg, int cc, int* S, int* ph, int* z) {
-  const XShape* sh = find_shape(mode, cg, cc);
-  const int t_wgs = btc_tune_get(BTC_TUNE_WGRAD_WGS);
-  const int wgs = t_wgs ? t_wgs : 512;
-  const int n_tiles = btc_cdiv(rows, TMX);
-  const int nz = (cg / (sh->mt * 16)) * btc_cdiv(cc, sh->nt * 16);
-  int p = sh->ph;
-  if (p > 1 && (long long)n_tiles * btc_cdiv(K, sh->kb * p) * nz < 3LL * wgs) p >>= 1;
-  const int groups = btc_cdiv(K, sh->kb * p);
-  int s = wgs / (groups * nz);
-  if (s > n_tiles / 2) s = n_tiles / 2;
-  if (s < 1) s = 1;
-  *S = s;
-  *ph = p;
-  if (z) *z = nz;
-  return groups;
-}
-
-int btc_launch_wgrad_x(int mode, const void* g, const void* c, const int32_t* map, const int32_t* ord, int rows, int K, int cg, int cc, float* part,
-                       int swap, hipStream_t stream) {
-  const XShape* sh = find_shape(mode, cg, cc);
-  BTC_CHECK_ARG(sh != nullptr && K <= 64, "btc_launch_wgrad_x: unsupported shape %d x %d (mode %d)", cg, cc, mode);
-  int S = 1, ph = 1, nz = 1;
-  const int groups = btc_wgrad_x_plan(mode, rows, K, cg, cc, &S, &ph, &nz);
-  dim3 grid(S, groups, nz);
+// bf: bf16 activations (MODE 0), else fp32 activations as split operands (MODE 1); w.Cg / w.Cc: channels of the gathered / contiguous operand
+bool btc_wgrad_x_plan(bool bf, int K, const WgradWalk& w, WgradLaunch* L) {
+  const int mode = bf ? 0 : 1;
+  const XTile* t = (w.rows >= 2048 && K >= 1 && K <= 64) ? find_shape(mode, w.Cg, w.Cc) : nullptr;
+  if (!t) return false;
+  const int ph[2] = {t->ph, t->ph / 2};
+  const int blocks = (w.Cg / (t->mt * 16)) * btc_cdiv(w.Cc, t->nt * 16);
+  const WgradSplit s = wgrad_split(btc_cdiv(w.rows, TMX), K, t->kb, ph, 2, blocks);
   const int t_depth = btc_tune_get(BTC_TUNE_WGRAD_X_DEPTH);
-  const bool shallow = t_depth ? t_depth == 1 : mode == 1;   // default: two items in flight for bf16 activations, one for split fp32
-#define X2(MT_, NT_, KB_, PH_, MODE_)                                                                            \
-  do {                                                                                                           \
-    if (shallow) launch_x<MT_, NT_, KB_, PH_, MODE_, 1>(grid, stream, g, c, map, ord, rows, K, cg, cc, part, swap);  \
-    else launch_x<MT_, NT_, KB_, PH_, MODE_, 2>(grid, stream, g, c, map, ord, rows, K, cg, cc, part, swap);          \
-  } while (0)
-#define X(MT_, NT_, KB_, PH_, MODE_)                                \
-  do {                                                              \
-    if (ph == PH_) X2(MT_, NT_, KB_, PH_, MODE_);                   \
-    else X2(MT_, NT_, KB_, (PH_ / 2), MODE_);                       \
-  } while (0)
-  const int mt = sh->mt, nt = sh->nt;
-  if (mode == 0) {
-    if (mt == 1 && nt == 1) X(1, 1, 4, 4, 0);
-    else if (mt == 2 && nt == 1) X(2, 1, 2, 8, 0);
-    else if (mt == 1 && nt == 2) X(1, 2, 4, 4, 0);
-    else if (mt == 2 && nt == 2) X(2, 2, 2, 8, 0);
-    else if (mt == 3 && nt == 2) X(3, 2, 2, 4, 0);
-    else if (mt == 2 && nt == 4) X(2, 4, 2, 4, 0);
-    else if (mt == 4 && nt == 2) X(4, 2, 1, 8, 0);
-    else X(4, 4, 1, 4, 0);
-  } else {
-    if (mt == 2 && nt == 1) X(2, 1, 2, 8, 1);
-    else if (mt == 1 && nt == 2) X(1, 2, 2, 8, 1);
-    else if (mt == 2 && nt == 2) X(2, 2, 2, 4, 1);
-    else if (mt == 3 && nt == 2) X(3, 2, 2, 2, 1);
-    else if (mt == 2 && nt == 4) X(2, 4, 2, 2, 1);
-    else if (mt == 4 && nt == 2) X(4, 2, 1, 4, 1);
-    else X(4, 4, 1, 2, 1);
-  }
-#undef X
-#undef X2
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  const int depth = (t_depth ? t_depth == 1 : mode == 1) ? 1 : 2;   // default: two items in flight for bf16 activations, one for split fp32
+  *L = WgradLaunch{};
+  L->family = WG_X;
+  L->S = s.S;
+  L->walk = w;
+  L->fn = t->fn[s.i][depth - 1];
+  L->lds = lds_x(t->mt, t->kb, s.ph, mode, depth);
+  L->groups = s.groups;
+  L->blocks = blocks;
+  return true;
 }

@@ -72,7 +72,7 @@ def _tuned(pairs, fn):
 
 
 def _applies(rb, n_src, cin, cout):
-    """btc_wgrad_n_kind + the row counts of conv_wgrad.hip wgrad_choose: narrow result (walk over the input rows) or narrow input (over the output rows)"""
+    """btc_wgrad_n_plan + the row counts of conv_wgrad.hip wgrad_choose: narrow result (walk over the input rows) or narrow input (over the output rows)"""
     K, n_out = rb.nbr_out.shape[1], rb.nbr_out.shape[0]
     if cout <= 8 and K * cout <= 176 and cin % 16 == 0:
         return n_src >= 2048

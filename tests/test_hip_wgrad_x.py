@@ -68,7 +68,7 @@ def _case(rng, cin, cout, kind, n_vox, shape=(12, 48, 44), B=2):
 
 
 SHAPES = [(32, 16), (16, 32), (32, 32), (48, 32), (32, 64), (64, 32), (64, 64), (128, 128), (256, 128), (192, 128), (64, 128), (32, 5), (64, 3)]
-# (mt, nt) tile shapes per mode, larger gathered blocks first (csrc/conv_wgrad_x.hip X_BF16 / X_SPLIT)
+# (mt, nt) tile shapes per mode, larger gathered blocks first (csrc/conv_wgrad_x.hip X_BF16_TILES / X_SPLIT_TILES)
 X_TILES = {0: [(4, 4), (4, 2), (2, 4), (3, 2), (2, 2), (2, 1), (1, 2), (1, 1)], 1: [(4, 4), (4, 2), (2, 4), (3, 2), (2, 2), (2, 1), (1, 2)]}
 
 
