@@ -1,5 +1,5 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
-include/btcdet_hip_bestmatch.h and include/btcdet_hip_frames.h).
+include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h and include/btcdet_hip_gtdb.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -223,6 +223,14 @@ _FRAMES_SIGS = {
 
 FRAMES_EXPORTED_SYMBOLS = tuple(_FRAMES_SIGS.keys())
 
+# the entry points of the sixth public header, include/btcdet_hip_gtdb.h (same library, same rules)
+_GTDB_SIGS = {
+    "btc_cut_objects_ws_bytes": (sz, [ci, ci, ci, ci]),
+    "btc_cut_objects": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+}
+
+GTDB_EXPORTED_SYMBOLS = tuple(_GTDB_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -234,7 +242,7 @@ def lib():
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
-                                  list(_FRAMES_SIGS.items())):
+                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

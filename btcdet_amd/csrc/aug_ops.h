@@ -1,9 +1,21 @@
-// The per-row pieces the augmentation kernels share (augment.hip, best_match.hip): the z rotation with its two roundings and the op
-// program of include/btcdet_hip_augment.h; the owner search over an ascending offsets array comes with compact.h.
+// The per-row pieces the augmentation kernels share (augment.hip, best_match.hip, gt_database.hip): the in-box test, the z rotation with
+// its two roundings and the op program of include/btcdet_hip_augment.h; the owner search over an ascending offsets array comes with
+// compact.h.
 #pragma once
 #include "compact.h"
 
 #include "../../include/btcdet_hip_augment.h"
+
+// database_sampler.points_in_boxes_mask against one (8) box row of device_augmentor.removal_rows: unfused float32 arithmetic (numpy
+// does not fuse, and a fused form moves a point that sits within an ulp of a face across it).  The removal of btc_augment_batch and
+// the cut of btc_cut_objects (include/btcdet_hip_gtdb.h) are this one function.
+static __device__ __forceinline__ bool aug_in_box(float x, float y, float z, const float* __restrict__ b) {
+  const float sx = __fsub_rn(x, b[0]), sy = __fsub_rn(y, b[1]);
+  const float c = b[6], s = b[7];
+  const float lx = __fsub_rn(__fmul_rn(sx, c), __fmul_rn(sy, s));
+  const float ly = __fadd_rn(__fmul_rn(sx, s), __fmul_rn(sy, c));
+  return (fabsf(__fsub_rn(z, b[2])) <= b[5]) && (fabsf(lx) < b[3]) && (fabsf(ly) < b[4]);
+}
 
 // data_side.rotate_points_along_z: p . [[c, s, 0], [-s, c, 0], [0, 0, 1]] with its two roundings
 static __device__ __forceinline__ void aug_rotate(float& x, float& y, float& z, float c, float s, bool small_set) {

@@ -18,21 +18,13 @@
 // All of it is a stream: a KITTI-shaped batch (2 x ~28 k rows of 16 bytes) is bound by its launches (mark, scan, offsets, emit:
 // 18.5 us in all, tools/augment_bench.py), a Waymo-shaped batch (2 x ~160 k rows) by HBM: 16 B read by aug_mark, 1 + 16 B read and 16 or 32 B written by aug_emit per row.  No atomics, no memset, no ticket: every
 // workspace word a kernel reads was written by an earlier launch of the same call.
-#include "aug_ops.h"   // aug_rotate, aug_run_ops: shared with best_match.hip; compact.h: the compaction's stages, aug_owner
+#include "aug_ops.h"   // aug_in_box (shared with gt_database.hip), aug_rotate, aug_run_ops (with best_match.hip); compact.h: the compaction's stages, aug_owner
 
 namespace {
 
 constexpr int AUG_T = BTC_COMPACT_T;
 constexpr int AUG_BOX_CHUNK = 64;
 constexpr int AUG_SMALL_SET = 45;   // rotate_points_along_z: sets below 45 rows (9 n < 400) take the rounded chain
-
-__device__ __forceinline__ bool aug_in_box(float x, float y, float z, const float* __restrict__ b) {
-  const float sx = __fsub_rn(x, b[0]), sy = __fsub_rn(y, b[1]);
-  const float c = b[6], s = b[7];
-  const float lx = __fsub_rn(__fmul_rn(sx, c), __fmul_rn(sy, s));
-  const float ly = __fadd_rn(__fmul_rn(sx, s), __fmul_rn(sy, c));
-  return (fabsf(__fsub_rn(z, b[2])) <= b[5]) && (fabsf(lx) < b[3]) && (fabsf(ly) < b[4]);
-}
 
 __global__ __launch_bounds__(AUG_T) void aug_mark(const float* __restrict__ pts, int n, int ld, const int32_t* __restrict__ scene_offsets,
                                                   int batch, const float* __restrict__ rm_boxes, const int32_t* __restrict__ rm_offsets,

@@ -199,7 +199,8 @@ class DataAugmentor(object):
 
 
 class ObjectBank(object):
-    """every object of a ground-truth database in one array: rows (sum n_i, F) float32, table path -> (first_row, n_rows)"""
+    """every object of a ground-truth database in one array: rows (sum n_i, F) float32, table path -> (first_row, n_rows).
+    ObjectBank(root, db_infos, F) reads one file per object; from_rows takes rows that exist already, on the host or on the device."""
 
     def __init__(self, root_path, db_infos, num_point_features):
         root = pathlib.Path(root_path)
@@ -216,7 +217,46 @@ class ObjectBank(object):
         self.rows = np.concatenate(parts, axis=0) if parts else np.zeros((0, self.num_point_features), np.float32)
         self._device = {}
 
+    @classmethod
+    def from_rows(cls, rows, table, num_point_features, device_rows=None):
+        """a bank from rows that are already in one array; reads no file.  rows (sum n_i, F) float32 on the host, or None with
+        device_rows: a (sum n_i, F) float32 tensor that is the bank on its device (gt_database.GtDatabase: the rows never left it) --
+        tensor() of that device returns it, and `rows` is copied from it on first host access."""
+        self = cls.__new__(cls)
+        self.num_point_features = int(num_point_features)
+        self.table = dict(table)
+        self._device, self._resident = {}, None
+        if device_rows is not None:
+            assert device_rows.dtype == torch.float32 and device_rows.dim() == 2 and device_rows.shape[1] == self.num_point_features
+            self._resident = device_rows.contiguous()
+        if rows is not None:
+            self.rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.num_point_features)
+            assert self._resident is None or self._resident.shape[0] == self.rows.shape[0]
+        elif self._resident is None:
+            raise ValueError("ObjectBank.from_rows: neither rows nor device_rows")
+        n_rows = self._resident.shape[0] if rows is None else self.rows.shape[0]
+        assert all(0 <= f and n >= 0 and f + n <= n_rows for f, n in self.table.values()), "a table entry outside the rows"
+        return self
+
+    @property
+    def rows(self):
+        if self._rows is None:
+            self._rows = self._resident.cpu().numpy()
+        return self._rows
+
+    @rows.setter
+    def rows(self, value):
+        self._rows = value
+
+    _rows = None
+    _resident = None
+
     def tensor(self, device):
+        res = self._resident
+        if res is not None:
+            want = torch.device(device)
+            if want.type == res.device.type and want.index in (None, res.device.index):
+                return res
         key = str(device)
         if key not in self._device:
             self._device[key] = torch.from_numpy(self.rows).to(device).contiguous()

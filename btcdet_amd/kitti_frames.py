@@ -10,8 +10,8 @@ What runs where: Calibration, scene() and the file reads are host work (O(boxes)
 points[fov_flag] over ~120 K rows per scan -- is btc_fov_crop (csrc/fov_crop.hip, include/btcdet_hip_frames.h), one stable compaction over
 the batch.  fov_crop_host() is the same step in the reference's numpy statements.
 
-Not here: creating the info pickles or the ground-truth database (get_infos, create_kitti_infos*, create_groundtruth_database), reading
-images (image shapes come from the infos), Waymo.
+Not here: creating the info pickles (get_infos, create_kitti_infos*), reading images (image shapes come from the infos), Waymo.  The
+ground-truth database is cut from these batches by btcdet_amd/gt_database.py.
 """
 import copy
 import os
