@@ -4,14 +4,19 @@
 // (spconv.SparseSequential, /root/reference/btcdet/models/backbones_3d/spconv_backbone.py:33-43,96,634): on ROCm that is
 // ~10 small launches per layer (statistics, running-stat updates, transform, clamp, and their backward twins), all
 // latency bound at BtcDet's sizes.  Here: 2 launches forward, 2 backward.
-//   bn_stats / bn_bwd_stats : per-workgroup partial channel sums (fp64 accumulation), and the LAST workgroup to
-//                             arrive (agent-scope release / acquire around one atomic ticket, cdna guide G16) reduces
-//                             the partials in index order (deterministic), updates the running statistics and
-//                             num_batches_tracked, and publishes mean / rstd (or dgamma / dbeta)
+//   bn_reduce               : the two-level, fixed-order channel reduction, stated once.  Every workgroup sums its rows per channel
+//                             (fp64 accumulation) and publishes the partial sums; the LAST workgroup to arrive (btc_last_arriver,
+//                             btc_common.h) adds every workgroup's partials in index order (deterministic), hands each channel's
+//                             totals to the caller and leaves the arrival counter zero for the next launch
+//   bn_stats / bn_bwd_stats / col_sum : bn_reduce with the kernel's own walk over a thread's rows (its unrolled and tail loops, its
+//                             arithmetic) and its own finalisation: mean / rstd, the running statistics and num_batches_tracked;
+//                             dgamma / dbeta; a plain sum.  The scalar and the 4-channels-per-thread path are one body (W = 1 / 4)
 //   bn_apply / bn_bwd_apply : elementwise, float4
 #include "btc_common.h"
 #include "bn_fuse.h"
 #include "../../include/btcdet_hip_infer.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -26,155 +31,148 @@ struct BnShape {
 // the activations the previous kernels wrote) once per workgroup (MI355X_MICROARCH.md, handoff-flag: `sc1` payload -> vmcnt(0) -> flag)
 __device__ __forceinline__ void st_partial(double* p, double v) { btc_st_agent(p, v); }
 
-// last-arriver election (placement independent: sc1 partials, drained -> ticket -> acquire)
-__device__ __forceinline__ bool last_block(int32_t* counter) {
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's partials have left its queue before the workgroup's ticket (btc_common.h)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = (btc_ticket_take(counter) == (int)gridDim.x - 1);
-  __syncthreads();
-  if (!s_last) return false;
-  if (threadIdx.x == 0) btc_ticket_acquire();
-  __syncthreads();
+// W adjacent channels of one row (W = 4: one float4, bf16: 8 bytes -- a quarter of the load instructions of W = 1 for the same bytes)
+template <bool BF, int W>
+__device__ __forceinline__ void bn_ld(const float* base, long long i, float (&e)[W]) {
+  if constexpr (W == 4) {
+    const float4 v = btc_ld4<BF>(base, i);
+    e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
+  } else {
+    e[0] = btc_ld1<BF>(base, i);
+  }
+}
+
+// one pass of a workgroup over the channel groups of shape S (W channels each, Q sums per channel): thread (cw, rr) fills its sums,
+// the row lanes 0 .. rpi-1 of a channel group are combined over LDS in that order, and row lane 0 emits the group's sums
+template <int W, int Q, int P, class Fill, class Emit>
+__device__ __forceinline__ void bn_pass(const BnShape& S, double (&s)[Q][P], Fill fill, Emit emit) {
+  const int tid = threadIdx.x;
+  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
+    const int cw = c0 + (tid % S.cpow), rr = tid / S.cpow;
+    double acc[Q][W];
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc[q][j] = 0.0;
+    if (cw < S.C) fill(cw, rr, acc);
+#pragma unroll
+    for (int j = 0; j < W; ++j)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) s[q][tid * W + j] = acc[q][j];
+    __syncthreads();
+    if (rr == 0 && cw < S.C) {
+      for (int l = 1; l < S.rpi; ++l)
+#pragma unroll
+        for (int j = 0; j < W; ++j)   // (channel outermost: in the other order the compiler keeps fewer LDS reads in flight)
+#pragma unroll
+          for (int q = 0; q < Q; ++q) acc[q][j] += s[q][(tid + l * S.cpow) * W + j];
+      emit(cw, acc);
+    }
+    __syncthreads();
+  }
+}
+
+// The reduction of Q sums per channel over all N rows.  S = bn_shape(N, C), SW = bn_shape(N, C / W): a thread owns W adjacent channels.
+//   rows(cw, r0, stride, acc) : adds rows r0, r0 + stride, ... (< N) of channels cw * W .. cw * W + W - 1 into acc[Q][W]
+//   done(c, t)                : the last workgroup's thread of channel c receives the totals t[Q]
+// partial[workgroup][q][c]; the last arriver's thread-row rr takes workgroups rr, rr + rpi, ... with D partials per sum in flight, added
+// as a tree (the walk is a chain of L2 round trips: at 4 in flight and 512 workgroups it took longer than the pass over the data -- 22
+// of the 45 us of a 210 K x 32 backward-statistics launch), then one at a time; the thread-rows are combined 0 .. rpi-1.
+// -> true in the last workgroup (all of it), after done() has run for every channel: once-per-launch work belongs behind it
+template <int W, int Q, int D, class Rows, class Done>
+__device__ __forceinline__ bool bn_reduce(const BnShape& S, const BnShape& SW, double* __restrict__ partial, int32_t* __restrict__ counter,
+                                          Rows rows, Done done) {
+  __shared__ double s[Q][BN_T * W];
+  const int G = (int)gridDim.x;
+  auto at = [&](int g, int q, int c) { return &partial[((size_t)g * Q + q) * S.C + c]; };
+  bn_pass<W>(SW, s,
+             [&](int cw, int rr, double (&acc)[Q][W]) { rows(cw, (long long)blockIdx.x * SW.rpi + rr, (long long)G * SW.rpi, acc); },
+             [&](int cw, double (&acc)[Q][W]) {
+#pragma unroll
+               for (int j = 0; j < W; ++j)
+#pragma unroll
+                 for (int q = 0; q < Q; ++q) st_partial(at(blockIdx.x, q, cw * W + j), acc[q][j]);
+             });
+  if (!btc_last_arriver(counter, G)) return false;
+  bn_pass<1>(S, s,
+             [&](int c, int rr, double (&acc)[Q][1]) {
+               int g = rr;
+               for (; g + (D - 1) * S.rpi < G; g += D * S.rpi) {
+                 double v[Q][D];
+#pragma unroll
+                 for (int u = 0; u < D; ++u)
+#pragma unroll
+                   for (int q = 0; q < Q; ++q) v[q][u] = btc_ld_agent(at(g + u * S.rpi, q, c));
+#pragma unroll
+                 for (int q = 0; q < Q; ++q) {
+#pragma unroll
+                   for (int h = 1; h < D; h *= 2)   // D = 8: ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7))
+#pragma unroll
+                     for (int u = 0; u < D; u += 2 * h) v[q][u] += v[q][u + h];
+                   acc[q][0] += v[q][0];
+                 }
+               }
+               for (; g < G; g += S.rpi)
+#pragma unroll
+                 for (int q = 0; q < Q; ++q) acc[q][0] += btc_ld_agent(at(g, q, c));
+             },
+             [&](int c, double (&acc)[Q][1]) {
+               double t[Q];
+#pragma unroll
+               for (int q = 0; q < Q; ++q) t[q] = acc[q][0];
+               done(c, t);
+             });
+  if (threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call on this stream
   return true;
 }
 
-// the last workgroup's sum over all workgroups' partial pairs, in a fixed order: thread-row rr takes workgroups rr, rr + rpi, ...
-// with 8 pairs in flight (the walk is a chain of L2 round trips: at 4 pairs in flight and 512 workgroups it took longer than the
-// pass over the data -- 22 of the 45 us of a 210 K x 32 backward-statistics launch)
-__device__ __forceinline__ void reduce_partials(const double* __restrict__ partial, int G, int C, int rpi, int c, int rr, double& a, double& b) {
-  int g = rr;
-  for (; g + 7 * rpi < G; g += 8 * rpi) {
-    double av[8], bv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      av[u] = btc_ld_agent(&partial[((size_t)(g + u * rpi) * 2 + 0) * C + c]);
-      bv[u] = btc_ld_agent(&partial[((size_t)(g + u * rpi) * 2 + 1) * C + c]);
-    }
-    a += ((av[0] + av[1]) + (av[2] + av[3])) + ((av[4] + av[5]) + (av[6] + av[7]));
-    b += ((bv[0] + bv[1]) + (bv[2] + bv[3])) + ((bv[4] + bv[5]) + (bv[6] + bv[7]));
-  }
-  for (; g < G; g += rpi) {
-    a += btc_ld_agent(&partial[((size_t)g * 2 + 0) * C + c]);
-    b += btc_ld_agent(&partial[((size_t)g * 2 + 1) * C + c]);
-  }
-}
-
-// partial[blk][0][c] = sum_x, partial[blk][1][c] = sum_x^2 over the block's rows
-// VEC: C % 4 == 0 -- a thread owns 4 adjacent channels and moves one float4 (bf16: 8 bytes) per row: a quarter of the load
-// instructions of the scalar walk for the same bytes (SV = the shape over C / 4 channel groups)
+// sum_x and sum_x^2 per channel; the last workgroup turns them into mean / rstd and the running statistics
 template <bool BF, bool VEC>
-__global__ __launch_bounds__(BN_T) void bn_stats(const float* __restrict__ x, BnShape S, BnShape SV, double* __restrict__ partial,
-                                                 int32_t* __restrict__ counter, float momentum, float eps, int training,
-                                                 const float* __restrict__ running_mean_in, float* __restrict__ running_mean,
+__global__ __launch_bounds__(BN_T) void bn_stats(const float* __restrict__ x, BnShape S, BnShape SW, double* __restrict__ partial,
+                                                 int32_t* __restrict__ counter, float momentum, float eps, float* __restrict__ running_mean,
                                                  float* __restrict__ running_var, long long* __restrict__ num_batches,
                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  __shared__ double s_a[BN_T * (VEC ? 4 : 1)], s_b[BN_T * (VEC ? 4 : 1)];
-  const int tid = threadIdx.x;
-  if (VEC) {
-    const int CV = S.C >> 2;
-    for (int cv0 = 0; cv0 < CV; cv0 += SV.cpow) {
-      const int cv = cv0 + (tid % SV.cpow), rr = tid / SV.cpow;
-      double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-      if (cv < CV) {
-        const long long stride = (long long)gridDim.x * SV.rpi;
-        long long r = (long long)blockIdx.x * SV.rpi + rr;
-        for (; r + 3 * stride < S.N; r += 4 * stride) {  // 4 independent 16-byte loads in flight
-          const float4 v0 = btc_ld4<BF>(x, r * S.C + cv * 4), v1 = btc_ld4<BF>(x, (r + stride) * S.C + cv * 4),
-                       v2 = btc_ld4<BF>(x, (r + 2 * stride) * S.C + cv * 4), v3 = btc_ld4<BF>(x, (r + 3 * stride) * S.C + cv * 4);
-          const float e0[4] = {v0.x, v0.y, v0.z, v0.w}, e1[4] = {v1.x, v1.y, v1.z, v1.w}, e2[4] = {v2.x, v2.y, v2.z, v2.w},
-                      e3[4] = {v3.x, v3.y, v3.z, v3.w};
+  constexpr int W = VEC ? 4 : 1;
+  const bool last = bn_reduce<W, 2, 8>(
+      S, SW, partial, counter,
+      [&](int cw, long long r, long long stride, double (&acc)[2][W]) {
+        const long long step = stride * S.C;   // elements between two of a thread's rows: uniform, so a thread keeps ONE element index
+        long long i = r * S.C + cw * W;
+        for (; r + 3 * stride < S.N; r += 4 * stride, i += 4 * step) {  // 4 independent loads (W = 4: of 16 bytes) in flight
+          float e0[W], e1[W], e2[W], e3[W];
+          bn_ld<BF>(x, i, e0);
+          bn_ld<BF>(x, i + step, e1);
+          bn_ld<BF>(x, i + 2 * step, e2);
+          bn_ld<BF>(x, i + 3 * step, e3);
+          // all four loads issue before the first is waited for (bf16 with W = 4: left alone, the scheduler waits for each load in turn
+          // to stay at 8 waves per SIMD)
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            a[j] += (double)e0[j] + (double)e1[j] + (double)e2[j] + (double)e3[j];
-            b[j] += (double)e0[j] * e0[j] + (double)e1[j] * e1[j] + (double)e2[j] * e2[j] + (double)e3[j] * e3[j];
+          for (int j = 0; j < W; ++j) {
+            acc[0][j] += (double)e0[j] + (double)e1[j] + (double)e2[j] + (double)e3[j];
+            acc[1][j] += (double)e0[j] * e0[j] + (double)e1[j] * e1[j] + (double)e2[j] * e2[j] + (double)e3[j] * e3[j];
           }
         }
-        for (; r < S.N; r += stride) {
-          const float4 v = btc_ld4<BF>(x, r * S.C + cv * 4);
-          const float e[4] = {v.x, v.y, v.z, v.w};
+        for (; r < S.N; r += stride, i += step) {
+          float e[W];
+          bn_ld<BF>(x, i, e);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { a[j] += e[j]; b[j] += (double)e[j] * e[j]; }
+          for (int j = 0; j < W; ++j) { acc[0][j] += e[j]; acc[1][j] += (double)e[j] * e[j]; }
         }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s_a[tid * 4 + j] = a[j]; s_b[tid * 4 + j] = b[j]; }
-      __syncthreads();
-      if (rr == 0 && cv < CV) {
-        for (int q = 1; q < SV.rpi; ++q)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { a[j] += s_a[(tid + q * SV.cpow) * 4 + j]; b[j] += s_b[(tid + q * SV.cpow) * 4 + j]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          st_partial(&partial[((size_t)blockIdx.x * 2 + 0) * S.C + cv * 4 + j], a[j]);
-          st_partial(&partial[((size_t)blockIdx.x * 2 + 1) * S.C + cv * 4 + j], b[j]);
+      },
+      [&](int c, const double (&t)[2]) {
+        double mean = t[0] / S.N;
+        double var = t[1] / S.N - mean * mean;  // biased, as F.batch_norm normalises with
+        if (var < 0.0) var = 0.0;
+        mean_out[c] = (float)mean;
+        rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
+        if (running_mean) {
+          double unb = S.N > 1 ? var * ((double)S.N / (double)(S.N - 1)) : var;
+          running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
+          running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
         }
-      }
-      __syncthreads();
-    }
-  } else
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0, b = 0.0;
-    if (c < S.C) {
-      const long long stride = (long long)gridDim.x * S.rpi;
-      long long r = (long long)blockIdx.x * S.rpi + rr;
-      for (; r + 3 * stride < S.N; r += 4 * stride) {  // 4 independent loads in flight
-        float v0 = btc_ld1<BF>(x, r * S.C + c), v1 = btc_ld1<BF>(x, (r + stride) * S.C + c), v2 = btc_ld1<BF>(x, (r + 2 * stride) * S.C + c),
-              v3 = btc_ld1<BF>(x, (r + 3 * stride) * S.C + c);
-        a += (double)v0 + (double)v1 + (double)v2 + (double)v3;
-        b += (double)v0 * v0 + (double)v1 * v1 + (double)v2 * v2 + (double)v3 * v3;
-      }
-      for (; r < S.N; r += stride) {
-        float v = btc_ld1<BF>(x, r * S.C + c);
-        a += v;
-        b += (double)v * v;
-      }
-    }
-    s_a[tid] = a;
-    s_b[tid] = b;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) {
-        a += s_a[tid + q * S.cpow];
-        b += s_b[tid + q * S.cpow];
-      }
-      st_partial(&partial[((size_t)blockIdx.x * 2 + 0) * S.C + c], a);
-      st_partial(&partial[((size_t)blockIdx.x * 2 + 1) * S.C + c], b);
-    }
-    __syncthreads();
-  }
-  if (!last_block(counter)) return;
-  // partials reduced in a fixed order: thread-row rr takes workgroups rr, rr + rpi, ...; rows combined 0..rpi-1
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0, b = 0.0;
-    if (c < S.C) reduce_partials(partial, (int)gridDim.x, S.C, S.rpi, c, rr, a, b);
-    s_a[tid] = a;
-    s_b[tid] = b;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) {
-        a += s_a[tid + q * S.cpow];
-        b += s_b[tid + q * S.cpow];
-      }
-      double mean = a / S.N;
-      double var = b / S.N - mean * mean;  // biased, as F.batch_norm normalises with
-      if (var < 0.0) var = 0.0;
-      mean_out[c] = (float)mean;
-      rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
-      if (running_mean) {
-        double unb = S.N > 1 ? var * ((double)S.N / (double)(S.N - 1)) : var;
-        running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-        running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-      }
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (num_batches) *num_batches += 1;
-    __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call on this stream
-  }
+      });
+  if (last && threadIdx.x == 0 && num_batches) *num_batches += 1;   // once per launch: the last workgroup only
 }
 
 __global__ __launch_bounds__(BN_T) void bn_eval_stats(const float* __restrict__ running_mean, const float* __restrict__ running_var,
@@ -208,131 +206,57 @@ __global__ __launch_bounds__(BN_T) void bn_apply(const float* __restrict__ x, co
   }
 }
 
-// partial sums of g = dy * (y > 0) and g * xhat; the last block turns them into dbeta / dgamma
+// sums of g = dy * (y > 0) and g * xhat per channel; the last workgroup turns them into dbeta / dgamma
 template <bool BF, bool VEC>
 __global__ __launch_bounds__(BN_T) void bn_bwd_stats(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
-                                                     const float* __restrict__ mean, const float* __restrict__ rstd, BnShape S, BnShape SV, int relu,
+                                                     const float* __restrict__ mean, const float* __restrict__ rstd, BnShape S, BnShape SW, int relu,
                                                      double* __restrict__ partial, int32_t* __restrict__ counter,
                                                      float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  __shared__ double s_a[BN_T * (VEC ? 4 : 1)], s_b[BN_T * (VEC ? 4 : 1)];
-  const int tid = threadIdx.x;
-  if (VEC) {
-    const int CV = S.C >> 2;
-    for (int cv0 = 0; cv0 < CV; cv0 += SV.cpow) {
-      const int cv = cv0 + (tid % SV.cpow), rr = tid / SV.cpow;
-      double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-      if (cv < CV) {
-        float m[4], rs[4];
+  constexpr int W = VEC ? 4 : 1, U = VEC ? 2 : 4;   // U rows of three streams at once: 6 16-byte or 12 4-byte loads in flight (latency bound)
+  bn_reduce<W, 2, 8>(
+      S, SW, partial, counter,
+      [&](int cw, long long r, long long stride, double (&acc)[2][W]) {
+        float m[W], rs[W];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { m[j] = mean[cv * 4 + j]; rs[j] = rstd[cv * 4 + j]; }
-        const long long stride = (long long)gridDim.x * SV.rpi;
-        long long r = (long long)blockIdx.x * SV.rpi + rr;
-        for (; r + stride < S.N; r += 2 * stride) {  // 6 independent 16-byte loads in flight
-          const long long i0 = r * S.C + cv * 4, i1 = (r + stride) * S.C + cv * 4;
-          const float4 g0 = btc_ld4<BF>(dy, i0), y0 = btc_ld4<BF>(y, i0), x0 = btc_ld4<BF>(x, i0);
-          const float4 g1 = btc_ld4<BF>(dy, i1), y1 = btc_ld4<BF>(y, i1), x1 = btc_ld4<BF>(x, i1);
-          const float gg[2][4] = {{g0.x, g0.y, g0.z, g0.w}, {g1.x, g1.y, g1.z, g1.w}};
-          const float yy[2][4] = {{y0.x, y0.y, y0.z, y0.w}, {y1.x, y1.y, y1.z, y1.w}};
-          const float xx[2][4] = {{x0.x, x0.y, x0.z, x0.w}, {x1.x, x1.y, x1.z, x1.w}};
+        for (int j = 0; j < W; ++j) { m[j] = mean[cw * W + j]; rs[j] = rstd[cw * W + j]; }
+        const long long step = stride * S.C;   // (as in bn_stats)
+        long long i = r * S.C + cw * W;
+        for (; r + (U - 1) * stride < S.N; r += U * stride, i += U * step) {
+          float gv[U][W], yv[U][W], xv[U][W];
 #pragma unroll
-          for (int u = 0; u < 2; ++u)
+          for (int u = 0; u < U; ++u) {
+            bn_ld<BF>(dy, i + u * step, gv[u]);
+            bn_ld<BF>(y, i + u * step, yv[u]);
+            bn_ld<BF>(x, i + u * step, xv[u]);
+          }
+          // (a row's terms are written out here and in the tail: through a shared lambda the bf16 W = 4 instance waits for four of its
+          // six loads before it issues the last two)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float g = (relu && !(yy[u][j] > 0.f)) ? 0.f : gg[u][j];
-              a[j] += (double)g;
-              b[j] += (double)g * ((xx[u][j] - m[j]) * rs[j]);
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+              const float g = (relu && !(yv[u][j] > 0.f)) ? 0.f : gv[u][j];
+              acc[0][j] += (double)g;
+              acc[1][j] += (double)g * ((xv[u][j] - m[j]) * rs[j]);
             }
         }
-        for (; r < S.N; r += stride) {
-          const long long i0 = r * S.C + cv * 4;
-          const float4 g0 = btc_ld4<BF>(dy, i0), y0 = btc_ld4<BF>(y, i0), x0 = btc_ld4<BF>(x, i0);
-          const float gg[4] = {g0.x, g0.y, g0.z, g0.w}, yy[4] = {y0.x, y0.y, y0.z, y0.w}, xx[4] = {x0.x, x0.y, x0.z, x0.w};
+        for (; r < S.N; r += stride, i += step) {
+          float gv[W], yv[W], xv[W];
+          bn_ld<BF>(dy, i, gv);
+          bn_ld<BF>(y, i, yv);
+          bn_ld<BF>(x, i, xv);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float g = (relu && !(yy[j] > 0.f)) ? 0.f : gg[j];
-            a[j] += (double)g;
-            b[j] += (double)g * ((xx[j] - m[j]) * rs[j]);
+          for (int j = 0; j < W; ++j) {
+            const float g = (relu && !(yv[j] > 0.f)) ? 0.f : gv[j];
+            acc[0][j] += (double)g;
+            acc[1][j] += (double)g * ((xv[j] - m[j]) * rs[j]);
           }
         }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s_a[tid * 4 + j] = a[j]; s_b[tid * 4 + j] = b[j]; }
-      __syncthreads();
-      if (rr == 0 && cv < CV) {
-        for (int q = 1; q < SV.rpi; ++q)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { a[j] += s_a[(tid + q * SV.cpow) * 4 + j]; b[j] += s_b[(tid + q * SV.cpow) * 4 + j]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          st_partial(&partial[((size_t)blockIdx.x * 2 + 0) * S.C + cv * 4 + j], a[j]);
-          st_partial(&partial[((size_t)blockIdx.x * 2 + 1) * S.C + cv * 4 + j], b[j]);
-        }
-      }
-      __syncthreads();
-    }
-  } else
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0, b = 0.0;
-    if (c < S.C) {
-      const float m = mean[c], rs = rstd[c];
-      const long long stride = (long long)gridDim.x * S.rpi;
-      long long r = (long long)blockIdx.x * S.rpi + rr;
-      for (; r + 3 * stride < S.N; r += 4 * stride) {  // 12 independent loads in flight (the kernel is latency bound)
-        float g[4], yv[4], xv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const long long i = (r + u * stride) * S.C + c;
-          g[u] = btc_ld1<BF>(dy, i);
-          yv[u] = btc_ld1<BF>(y, i);
-          xv[u] = btc_ld1<BF>(x, i);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (relu && !(yv[u] > 0.f)) g[u] = 0.f;
-          a += (double)g[u];
-          b += (double)g[u] * ((xv[u] - m) * rs);
-        }
-      }
-      for (; r < S.N; r += stride) {
-        float g = btc_ld1<BF>(dy, r * S.C + c);
-        if (relu && !(btc_ld1<BF>(y, r * S.C + c) > 0.f)) g = 0.f;
-        a += g;
-        b += (double)g * ((btc_ld1<BF>(x, r * S.C + c) - m) * rs);
-      }
-    }
-    s_a[tid] = a;
-    s_b[tid] = b;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) {
-        a += s_a[tid + q * S.cpow];
-        b += s_b[tid + q * S.cpow];
-      }
-      st_partial(&partial[((size_t)blockIdx.x * 2 + 0) * S.C + c], a);
-      st_partial(&partial[((size_t)blockIdx.x * 2 + 1) * S.C + c], b);
-    }
-    __syncthreads();
-  }
-  if (!last_block(counter)) return;
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0, b = 0.0;
-    if (c < S.C) reduce_partials(partial, (int)gridDim.x, S.C, S.rpi, c, rr, a, b);
-    s_a[tid] = a;
-    s_b[tid] = b;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) {
-        a += s_a[tid + q * S.cpow];
-        b += s_b[tid + q * S.cpow];
-      }
-      dbeta[c] = (float)a;
-      dgamma[c] = (float)b;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      },
+      [&](int c, const double (&t)[2]) {
+        dbeta[c] = (float)t[0];
+        dgamma[c] = (float)t[1];
+      });
 }
 
 template <bool VEC, bool BF>
@@ -372,48 +296,21 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply(const float* __restrict__ x
   else btc_st1<BF>(dx, i, o[0]);
 }
 
-// column sums of an (N, C) matrix (the bias gradient of a sparse conv): same two-level, fixed-order scheme as bn_bwd_stats
+// column sums of an (N, C) matrix (the bias gradient of a sparse conv): bn_reduce with one sum per channel, one partial in flight
 template <bool BF>
 __global__ __launch_bounds__(BN_T) void col_sum(const float* __restrict__ x, BnShape S, double* __restrict__ partial,
                                                 int32_t* __restrict__ counter, float* __restrict__ out) {
-  __shared__ double s_a[BN_T];
-  const int tid = threadIdx.x;
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0;
-    if (c < S.C) {
-      const long long stride = (long long)gridDim.x * S.rpi;
-      long long r = (long long)blockIdx.x * S.rpi + rr;
-      for (; r + 3 * stride < S.N; r += 4 * stride) {
-        float v0 = btc_ld1<BF>(x, r * S.C + c), v1 = btc_ld1<BF>(x, (r + stride) * S.C + c), v2 = btc_ld1<BF>(x, (r + 2 * stride) * S.C + c),
-              v3 = btc_ld1<BF>(x, (r + 3 * stride) * S.C + c);
-        a += ((double)v0 + (double)v1) + ((double)v2 + (double)v3);
-      }
-      for (; r < S.N; r += stride) a += (double)btc_ld1<BF>(x, r * S.C + c);
-    }
-    s_a[tid] = a;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) a += s_a[tid + q * S.cpow];
-      st_partial(&partial[(size_t)blockIdx.x * S.C + c], a);
-    }
-    __syncthreads();
-  }
-  if (!last_block(counter)) return;
-  for (int c0 = 0; c0 < S.C; c0 += S.cpow) {
-    const int c = c0 + (tid % S.cpow), rr = tid / S.cpow;
-    double a = 0.0;
-    if (c < S.C)
-      for (int g = rr; g < (int)gridDim.x; g += S.rpi) a += btc_ld_agent(&partial[(size_t)g * S.C + c]);
-    s_a[tid] = a;
-    __syncthreads();
-    if (rr == 0 && c < S.C) {
-      for (int q = 1; q < S.rpi; ++q) a += s_a[tid + q * S.cpow];
-      out[c] = (float)a;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  bn_reduce<1, 1, 1>(
+      S, S, partial, counter,
+      [&](int c, long long r, long long stride, double (&acc)[1][1]) {
+        for (; r + 3 * stride < S.N; r += 4 * stride) {
+          float v0 = btc_ld1<BF>(x, r * S.C + c), v1 = btc_ld1<BF>(x, (r + stride) * S.C + c), v2 = btc_ld1<BF>(x, (r + 2 * stride) * S.C + c),
+                v3 = btc_ld1<BF>(x, (r + 3 * stride) * S.C + c);
+          acc[0][0] += ((double)v0 + (double)v1) + ((double)v2 + (double)v3);
+        }
+        for (; r < S.N; r += stride) acc[0][0] += (double)btc_ld1<BF>(x, r * S.C + c);
+      },
+      [&](int c, const double (&t)[1]) { out[c] = (float)t[0]; });
 }
 
 BnShape bn_shape(int N, int C) {
@@ -452,6 +349,21 @@ int bn_grid_bytes(long long bytes, int tune_key, int kb_default) {
   return (int)(g > 256 ? 256 : (g < 1 ? 1 : g));
 }
 
+// the workspace of every entry point below (btc_bn_ws_bytes): the first 256 bytes hold the arrival counter, zero on entry and zero on
+// exit; the partial sums behind it may hold anything
+struct BnWs {
+  int32_t* counter;
+  double* partial;
+  explicit BnWs(void* ws) : counter((int32_t*)ws), partial((double*)((char*)ws + 256)) {}
+};
+
+// the one choice of channels per thread: W = 4 when C % 4 == 0 (16-byte moves, bf16: 8), else 1.  f(W as a constant, SW) launches
+template <class F>
+int bn_by_width(int N, int C, F&& f) {
+  if ((C & 3) == 0) return f(std::integral_constant<int, 4>(), bn_shape(N, C >> 2));
+  return f(std::integral_constant<int, 1>(), bn_shape(N, C));
+}
+
 }  // namespace
 
 extern "C" size_t btc_bn_ws_bytes(int C) { return 256 + btc_align((size_t)512 * 2 * C * sizeof(double)); }
@@ -459,74 +371,62 @@ extern "C" size_t btc_bn_ws_bytes(int C) { return 256 + btc_align((size_t)512 * 
 template <bool BF>
 static int bn_fwd_impl(const float* x, int N, int C, const float* gamma, const float* beta, float* running_mean,
                                float* running_var, long long* num_batches_tracked, float momentum, float eps, int training, int relu,
-                               float* y, float* save_mean, float* save_rstd, void* ws, size_t ws_bytes, void* stream_, bool have_stats = false) {
+                               float* y, float* save_mean, float* save_rstd, void* ws_, size_t ws_bytes, void* stream_, bool have_stats = false) {
   // have_stats: save_mean / save_rstd (and the running statistics) were produced by the conv kernel's epilogue (bn_fuse.h): apply only
   hipStream_t stream = (hipStream_t)stream_;
   BTC_CHECK_ARG(N >= 1 && C >= 1, "btc_bn_relu_fwd: empty input");
   BTC_CHECK_ARG(ws_bytes >= btc_bn_ws_bytes(C), "btc_bn_relu_fwd: workspace too small");
   BTC_CHECK_ARG(training || (running_mean && running_var), "btc_bn_relu_fwd: eval mode needs running statistics");
-  int32_t* counter = (int32_t*)ws;  // first 256 bytes: arrival counter, zero on entry, zero on exit
-  double* partial = (double*)((char*)ws + 256);
-  BnShape S = bn_shape(N, C);
-  if (have_stats) {
-  } else if (training) {
-    if ((C & 3) == 0) {
-      const BnShape SV = bn_shape(N, C >> 2);
-      const int g = bn_grid_bytes((long long)N * C * (BF ? 2 : 4), BTC_TUNE_BN_FWD_KB, 64);
-      bn_stats<BF, true><<<g, BN_T, 0, stream>>>(x, S, SV, partial, counter, momentum, eps, training, running_mean, running_mean, running_var,
-                                                 num_batches_tracked, save_mean, save_rstd);
-    } else {
-      bn_stats<BF, false><<<bn_grid(N, S), BN_T, 0, stream>>>(x, S, S, partial, counter, momentum, eps, training, running_mean, running_mean,
-                                                          running_var, num_batches_tracked, save_mean, save_rstd);
+  const BnWs ws(ws_);
+  const BnShape S = bn_shape(N, C);
+  const long long total = (long long)N * C;
+  return bn_by_width(N, C, [&](auto w, const BnShape& SW) {
+    constexpr int W = decltype(w)::value;
+    if (!have_stats && training) {
+      const int g = W == 4 ? bn_grid_bytes(total * (BF ? 2 : 4), BTC_TUNE_BN_FWD_KB, 64) : bn_grid(N, S);
+      bn_stats<BF, W == 4><<<g, BN_T, 0, stream>>>(x, S, SW, ws.partial, ws.counter, momentum, eps, running_mean, running_var,
+                                                    num_batches_tracked, save_mean, save_rstd);
+    } else if (!have_stats) {
+      bn_eval_stats<<<btc_cdiv(C, BN_T), BN_T, 0, stream>>>(running_mean, running_var, C, eps, save_mean, save_rstd);
     }
-  } else {
-    bn_eval_stats<<<btc_cdiv(C, BN_T), BN_T, 0, stream>>>(running_mean, running_var, C, eps, save_mean, save_rstd);
-  }
-  BTC_LAUNCH_CHECK();
-  long long total = (long long)N * C;
-  if ((C & 3) == 0) bn_apply<true, BF><<<btc_cdiv(total / 4, BN_T), BN_T, 0, stream>>>(x, save_mean, save_rstd, gamma, beta, total, C, relu, y);
-  else bn_apply<false, BF><<<btc_cdiv(total, BN_T), BN_T, 0, stream>>>(x, save_mean, save_rstd, gamma, beta, total, C, relu, y);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+    BTC_LAUNCH_CHECK();
+    bn_apply<W == 4, BF><<<btc_cdiv(total / W, BN_T), BN_T, 0, stream>>>(x, save_mean, save_rstd, gamma, beta, total, C, relu, y);
+    BTC_LAUNCH_CHECK();
+    return BTC_OK;
+  });
 }
 
 template <bool BF>
 static int bn_bwd_impl(const float* x, const float* y, const float* dy, int N, int C, const float* gamma, const float* save_mean,
-                               const float* save_rstd, int training, int relu, float* dx, float* dgamma, float* dbeta, void* ws,
+                               const float* save_rstd, int training, int relu, float* dx, float* dgamma, float* dbeta, void* ws_,
                                size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   BTC_CHECK_ARG(N >= 1 && C >= 1, "btc_bn_relu_bwd: empty input");
   BTC_CHECK_ARG(ws_bytes >= btc_bn_ws_bytes(C), "btc_bn_relu_bwd: workspace too small");
-  int32_t* counter = (int32_t*)ws;
-  double* partial = (double*)((char*)ws + 256);
-  BnShape S = bn_shape(N, C);
-  if ((C & 3) == 0) {
-    const BnShape SV = bn_shape(N, C >> 2);
-    const int g = bn_grid_bytes((long long)N * C * (BF ? 6 : 12), BTC_TUNE_BN_BWD_KB, 128);
-    bn_bwd_stats<BF, true><<<g, BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, S, SV, relu, partial, counter, dgamma, dbeta);
-  } else {
-    bn_bwd_stats<BF, false><<<bn_grid_bwd(N, S), BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, S, S, relu, partial, counter, dgamma, dbeta);
-  }
-  BTC_LAUNCH_CHECK();
-  long long total = (long long)N * C;
-  if ((C & 3) == 0)
-    bn_bwd_apply<true, BF><<<btc_cdiv(total / 4, BN_T), BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, gamma, dgamma, dbeta, total, C, N, relu,
-                                                                      training, dx);
-  else
-    bn_bwd_apply<false, BF><<<btc_cdiv(total, BN_T), BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, gamma, dgamma, dbeta, total, C, N, relu,
-                                                                   training, dx);
-  BTC_LAUNCH_CHECK();
-  return BTC_OK;
+  const BnWs ws(ws_);
+  const BnShape S = bn_shape(N, C);
+  const long long total = (long long)N * C;
+  return bn_by_width(N, C, [&](auto w, const BnShape& SW) {
+    constexpr int W = decltype(w)::value;
+    const int g = W == 4 ? bn_grid_bytes(total * (BF ? 6 : 12), BTC_TUNE_BN_BWD_KB, 128) : bn_grid_bwd(N, S);
+    bn_bwd_stats<BF, W == 4><<<g, BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, S, SW, relu, ws.partial, ws.counter, dgamma, dbeta);
+    BTC_LAUNCH_CHECK();
+    bn_bwd_apply<W == 4, BF><<<btc_cdiv(total / W, BN_T), BN_T, 0, stream>>>(x, y, dy, save_mean, save_rstd, gamma, dgamma, dbeta, total, C, N,
+                                                                             relu, training, dx);
+    BTC_LAUNCH_CHECK();
+    return BTC_OK;
+  });
 }
 
 // out[c] = sum over rows of x[r][c] (fp64 accumulation, deterministic).  ws as for btc_bn_relu_fwd.
 template <bool BF>
-static int col_sum_impl(const float* x, int N, int C, float* out, void* ws, size_t ws_bytes, void* stream_) {
+static int col_sum_impl(const float* x, int N, int C, float* out, void* ws_, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   BTC_CHECK_ARG(N >= 1 && C >= 1, "btc_col_sum: empty input");
   BTC_CHECK_ARG(ws_bytes >= btc_bn_ws_bytes(C), "btc_col_sum: workspace too small");
-  BnShape S = bn_shape(N, C);
-  col_sum<BF><<<bn_grid_bwd(N, S), BN_T, 0, stream>>>(x, S, (double*)((char*)ws + 256), (int32_t*)ws, out);
+  const BnWs ws(ws_);
+  const BnShape S = bn_shape(N, C);
+  col_sum<BF><<<bn_grid_bwd(N, S), BN_T, 0, stream>>>(x, S, ws.partial, ws.counter, out);
   BTC_LAUNCH_CHECK();
   return BTC_OK;
 }

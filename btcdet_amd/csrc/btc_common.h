@@ -37,7 +37,10 @@ void btc_set_error(const char* fmt, ...);
     }                                                                             \
   } while (0)
 
-// ---- last-arriver reductions: ONE statement of the protocol (bn.hip, bn_fuse.h, rulebook.hip rb_scan, occ_loss.hip, glue.hip sumsq2) ----
+// ---- last-arriver reductions: ONE statement of the protocol ----
+// users: through btc_last_arriver (below) bn.hip bn_reduce, occ_loss.hip occ_loss_fwd, det_post.hip det_select_nms, occ_metrics.hip
+// occ_points; with a sequence of their own bn_fuse.h bn_fuse_finish (its kernels run at the dynamic-LDS limit and pass their own flag
+// word), glue.hip sumsq2 and rulebook.hip scan_chunk (only thread 0 stores a payload, so only it drains and takes the ticket: cheaper)
 // producers : publish their partial results with agent-scope relaxed stores / atomics (btc_st_agent, unsafeAtomicAdd: `sc1` operations,
 //             performed at the device's coherence point, never left dirty in one XCD's L2), then btc_ticket_take(): drain the wave's
 //             vector-memory queue (s_waitcnt vmcnt(0)) and take a relaxed agent-scope ticket;
@@ -63,6 +66,20 @@ __device__ __forceinline__ int btc_ticket_take(int32_t* counter) {
   return __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void btc_ticket_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+// the election for a workgroup whose waves ALL publish (called by every thread of each of the `total` workgroups that share `counter`):
+// every wave drains its own stores, the workgroup meets, thread 0 takes the workgroup's ticket and publishes the verdict through one LDS
+// word; in the last workgroup thread 0 acquires and the workgroup meets again.  -> true in the last workgroup (all of it)
+__device__ __forceinline__ bool btc_last_arriver(int32_t* counter, int total) {
+  __shared__ int s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's partials have left its queue before the workgroup's ticket
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = (btc_ticket_take(counter) == total - 1);
+  __syncthreads();
+  if (!s_last) return false;
+  if (threadIdx.x == 0) btc_ticket_acquire();
+  __syncthreads();
+  return true;
+}
 #endif
 
 // tuning overrides (btc_tune_set): 0 = built-in policy

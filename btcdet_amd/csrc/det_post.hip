@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void det_select_nms(SelArgs a) {
   __shared__ unsigned short s_order[DET_MAX_N];     // sorted position -> input index
   __shared__ u64 s_remv[DET_WORDS];
   __shared__ u64 s_kept;
-  __shared__ int s_count, s_last;
+  __shared__ int s_count;
   const int s = blockIdx.y, rb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* cls = a.cls + (size_t)s * a.n * a.C;
   const float* boxes = a.boxes + (size_t)s * a.n * a.stride;
@@ -120,16 +120,10 @@ __global__ __launch_bounds__(256) void det_select_nms(SelArgs a) {
       btc_st_agent(mask + (size_t)row * a.words + cb, t);
     }
   }
-  // 4. last-arriver hand-over (btc_common.h): every storing wave drains its stores, the workgroup meets, one lane takes the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) s_last = (btc_ticket_take(a.tickets + s) == (int)gridDim.x - 1);
-  __syncthreads();
-  if (!s_last) return;
-  if (tid == 0) {
-    btc_ticket_acquire();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  // 4. last-arriver hand-over (btc_common.h) among the scene's workgroups; the acquiring lane then waits for its invalidate before the
+  //    workgroup meets again below
+  if (!btc_last_arriver(a.tickets + s, (int)gridDim.x)) return;
+  if (tid == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (tid < DET_WORDS) s_remv[tid] = 0ull;
   __syncthreads();
   // 5. the greedy chain, 64 candidates at a time (as nms_reduce of iou3d_nms.hip), stopped at post_max kept boxes

@@ -17,18 +17,6 @@ struct LossParams {
   float beta, eps, w_cls, w_res;
 };
 
-__device__ __forceinline__ bool last_block_l(int32_t* counter) {
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = (btc_ticket_take(counter) == (int)gridDim.x - 1);   // (the protocol: btc_common.h)
-  __syncthreads();
-  if (!s_last) return false;
-  if (threadIdx.x == 0) btc_ticket_acquire();
-  __syncthreads();
-  return true;
-}
-
 // per-cell terms; returns weighted losses
 __device__ __forceinline__ void cell_terms(const float* __restrict__ logit, const float* __restrict__ res, const float* __restrict__ tgt,
                                            const LossParams& P, int b, long long sp, int pos, float* fl, float sl[3]) {
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(256) void occ_loss_fwd(const float* __restrict__ lo
     double v = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
     btc_st_agent(&partial[(size_t)blockIdx.x * 4 + threadIdx.x], v);
   }
-  if (!last_block_l(counter)) return;
+  if (!btc_last_arriver(counter, (int)gridDim.x)) return;   // (the protocol: btc_common.h)
   // the last workgroup: thread t sums quantity t % 4 over blocks t / 4, t / 4 + 64, ... in order, then a fixed tree over the 64 threads
   // of each quantity (one thread walking every block's four partials was most of this launch)
   {

@@ -124,7 +124,7 @@ __device__ __forceinline__ int occ_valid_boxes(const PointArgs& a, int b) { retu
 
 __global__ __launch_bounds__(OCC_BLOCK) void occ_points(PointArgs a) {
   __shared__ float s_box[OCC_BOX_CHUNK][8];   // cx cy cz hx hy hz cos sin
-  __shared__ int s_lo, s_hi, s_last;
+  __shared__ int s_lo, s_hi;
   __shared__ unsigned s_cnt[OCC_N_THRESH];
   __shared__ u64 s_boxes;
   const int tid = threadIdx.x;
@@ -174,14 +174,10 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_points(PointArgs a) {
       __syncthreads();
     }
   }
-  // last-arriver hand-over (btc_common.h): the atomics are drained, the workgroup meets, one lane takes the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) s_last = (btc_ticket_take(a.ws.ticket) == (int)gridDim.x - 1);
-  __syncthreads();
-  if (!s_last) return;
+  // last-arriver hand-over (btc_common.h): the payload here is the atomics; the acquiring lane then waits for its invalidate before
+  // the workgroup meets again below
+  if (!btc_last_arriver(a.ws.ticket, (int)gridDim.x)) return;
   if (tid == 0) {
-    btc_ticket_acquire();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     s_boxes = 0ull;
   }
