@@ -1,5 +1,5 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
-include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h and include/btcdet_hip_gtdb.h).
+include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h and include/btcdet_hip_templates.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -231,6 +231,17 @@ _GTDB_SIGS = {
 
 GTDB_EXPORTED_SYMBOLS = tuple(_GTDB_SIGS.keys())
 
+# the entry points of the seventh public header, include/btcdet_hip_templates.h (same library, same rules)
+cf = ctypes.c_float
+_TEMPLATES_SIGS = {
+    "btc_nn_sqdist": (ci, [vp, ci, vp, ci, vp, vp, ci, ci, vp, vp]),
+    "btc_match_candidates": (ci, [vp, ci, vp, vp, ci, vp, vp, ci, ci, cf, cf, cf, ci, ci, vp, vp, vp]),
+    "btc_select_templates_ws_bytes": (sz, [ci, ci, ci]),
+    "btc_select_templates": (ci, [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+TEMPLATES_EXPORTED_SYMBOLS = tuple(_TEMPLATES_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -242,7 +253,7 @@ def lib():
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
-                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items())):
+                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -305,11 +305,53 @@ class TemplateBank(object):
         self.rows = np.ascontiguousarray(np.concatenate(parts, axis=0), dtype=np.float32) if parts else np.zeros((0, 3), np.float32)
         self._device = {}
 
+    @classmethod
+    def from_rows(cls, rows, table, device_rows=None, load_point_features=3):
+        """a bank from rows that are already in one array, beside ObjectBank.from_rows; reads no file.  table: (class name, image_idx,
+        gt_idx) -> (first_row, n_rows).  rows (sum n_i, 3) float32 on the host, or None with device_rows: a (sum n_i, 3) float32 tensor
+        that is the bank on its device (template_builder.TemplateBuilder: the rows never left it) -- tensor() of that device returns
+        it, and `rows` is copied from it on first host access."""
+        self = cls.__new__(cls)
+        self.load_point_features = int(load_point_features)
+        self.table = {(str(n), int(i), int(g)): (int(f), int(c)) for (n, i, g), (f, c) in table.items()}
+        self._device, self._resident = {}, None
+        if device_rows is not None:
+            assert device_rows.dtype == torch.float32 and device_rows.dim() == 2 and device_rows.shape[1] == 3
+            self._resident = device_rows.contiguous()
+        if rows is not None:
+            self.rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 3)
+            assert self._resident is None or self._resident.shape[0] == self.rows.shape[0]
+        elif self._resident is None:
+            raise ValueError("TemplateBank.from_rows: neither rows nor device_rows")
+        n_rows = self._resident.shape[0] if rows is None else self.rows.shape[0]
+        assert n_rows < 2 ** 31, "template rows are addressed with int32"
+        assert all(0 <= f and n >= 0 and f + n <= n_rows for f, n in self.table.values()), "a table entry outside the rows"
+        return self
+
+    @property
+    def rows(self):
+        if self._rows is None:
+            self._rows = self._resident.cpu().numpy()
+        return self._rows
+
+    @rows.setter
+    def rows(self, value):
+        self._rows = value
+
+    _rows = None
+    _resident = None
+
     @property
     def nbytes(self):
-        return int(self.rows.nbytes)
+        res = self._resident
+        return int(self.rows.nbytes) if res is None else int(res.numel() * res.element_size())
 
     def tensor(self, device):
+        res = self._resident
+        if res is not None:
+            want = torch.device(device)
+            if want.type == res.device.type and want.index in (None, res.device.index):
+                return res
         key = str(device)
         if key not in self._device:
             self._device[key] = torch.from_numpy(self.rows).to(device).contiguous()
