@@ -641,7 +641,8 @@ int btc_nms(const float* boxes_sorted, int n, float thresh, int rotated, long lo
  *     voxel (x, y, z), stride_zyx, grid_dhw of the sparse tensor; cell_row (batch, D, H, W) i32 = row of the cell or -1 ->
  *     rows (n_points, 8) i32 (corner order dz, dy, dx; -1 = empty / outside), weights (n_points, 8) f32 (|w|, 0 where no row),
  *     flag (n_points) u8 = some corner contributes; row_live (n_rows) u8 or NULL: rows with a non-zero entry -- the reference keeps a
- *     point iff its interpolated vector has one, so an all-zero row is read (and receives its gradient) but keeps no point alive
+ *     point iff its interpolated vector has one, so an all-zero row is read (and receives its gradient) but keeps no point alive.
+ *     Trailing points past batch * points_per_batch read nothing (rows -1, weights 0, flag 0).
  *   btc_trilinear_gather: rows / weights (n_keep, 8) of the KEPT points -> out (n_keep, C) = sum_c weights[p][c] * feat[rows[p][c]] in
  *     corner order
  *   btc_trilinear_scatter: the adjoint, deterministic: pair_sorted (n_pairs) i32 = the (point, corner) pairs e = 8 p + c stably sorted by
