@@ -10,11 +10,14 @@ Voxelizer, occupancy/occlusion target generator, sparse-3D-conv rulebook + fused
 * ``btcdet_amd.kitti_frames``   -- ``KittiFrames`` / ``Calibration``: a KITTI directory into a resident batch, the FOV crop on the GPU
 * ``btcdet_amd.gt_database``    -- ``GtDatabase``: the ground-truth database of ``gt_sampling`` cut from resident scans, its bank resident
 * ``btcdet_amd.template_builder`` -- ``TemplateBuilder``: the best-match templates made from resident databases, their bank resident
+* ``btcdet_amd.kitti_infos``    -- ``KittiInfoBuilder`` / ``add_coverage``: the info pickles from a raw KITTI directory, points per box and
+  coverage cells counted on the GPU
 * ``btcdet_amd.occ_targets``    -- ``OccTargets3D`` (occupancy / occlusion grid generator)
 * ``btcdet_amd.vfe`` / ``backbones_3d`` / ``occ_head`` / ``pass_occ_vox`` / ``height_compression``
 
 All compute goes through ``libbtcdet_hip.so`` (hand-written HIP, C ABI in ``include/btcdet_hip.h``, ``btcdet_hip_infer.h``,
-``btcdet_hip_augment.h``, ``btcdet_hip_bestmatch.h``, ``btcdet_hip_frames.h``, ``btcdet_hip_gtdb.h``, ``btcdet_hip_templates.h``).
+``btcdet_hip_augment.h``, ``btcdet_hip_bestmatch.h``, ``btcdet_hip_frames.h``, ``btcdet_hip_gtdb.h``, ``btcdet_hip_templates.h``,
+``btcdet_hip_infos.h``).
 """
 __version__ = "0.1.0"
 

@@ -13,6 +13,7 @@
 // A stream: 16 B read by fov_mark, 1 + 16 B read and at most 16 + 4 B written by fov_scatter per row of a (n, 4) scan.  No atomics, no
 // memset, no ticket: every workspace word a kernel reads was written by an earlier launch of the same call.
 #include "compact.h"   // the compaction's count, rank, boundary, row copy and workspace; aug_owner
+#include "fov_keep.h"  // the per-row decision (the header's arithmetic), shared with kitti_infos.hip
 
 #include "../../include/btcdet_hip_frames.h"
 
@@ -21,22 +22,6 @@ namespace {
 constexpr int FOV_T = BTC_COMPACT_T;
 constexpr int FOV_CAL = BTC_FOV_CALIB_FLOATS;
 constexpr int FOV_CHUNK = FOV_T / FOV_CAL;   // calibration blocks staged per pass: one float per thread
-
-// the header's arithmetic; c = one scene's calibration block
-__device__ __forceinline__ bool fov_keep(float x, float y, float z, const float* __restrict__ c) {
-  float r[3], h[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    r[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, c[j]), __fmul_rn(y, c[3 + j])), __fmul_rn(z, c[6 + j])), c[9 + j]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float* p = c + 12 + 4 * i;
-    h[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r[0], p[0]), __fmul_rn(r[1], p[1])), __fmul_rn(r[2], p[2])), p[3]);
-  }
-  const float u = __fdiv_rn(h[0], r[2]), v = __fdiv_rn(h[1], r[2]);
-  const float depth = __fsub_rn(h[2], c[12 + 11]);
-  return (u >= 0.f) & (u < c[24]) & (v >= 0.f) & (v < c[25]) & (depth >= 0.f);   // NaN compares false, as in numpy
-}
 
 template <bool VEC4>
 __global__ __launch_bounds__(FOV_T) void fov_mark(const float* __restrict__ pts, int n, int ld, const int32_t* __restrict__ scene_offsets, int batch,

@@ -20,71 +20,14 @@
 // written by an earlier launch of the same call.  Every index formed from a device array is clamped to n, m, max_boxes, the tile
 // bound or out_capacity before it addresses anything.
 #include "aug_ops.h"   // aug_in_box; compact.h: aug_owner, btc_aligned16, BTC_COMPACT_T
+#include "scene_tiles.h"   // GT_T, gtdb_span, gtdb_tiles, GtTile, gtdb_tile, gtdb_load, gtdb_tmax: shared with kitti_infos.hip
 
 #include "../../include/btcdet_hip_gtdb.h"
 
 namespace {
 
-constexpr int GT_T = BTC_COMPACT_T;
 constexpr int GT_WAVES = GT_T / 64;
 constexpr int GT_BOX_CHUNK = 64;   // boxes staged per pass: one per lane of a wave, one bit of a 64-bit mask
-
-// set s of an offsets array as [lo, hi), clamped to [0, limit] and to ascending order
-__device__ __forceinline__ void gtdb_span(const int32_t* __restrict__ offs, int s, int limit, int& lo, int& hi) {
-  lo = min(max(offs[s], 0), limit);
-  hi = min(max(offs[s + 1], lo), limit);
-}
-
-// tile_first[s] = tiles in front of scene s, tile_first[batch] = all of them; never above tmax
-__global__ __launch_bounds__(64) void gtdb_tiles(const int32_t* __restrict__ scene_offsets, int batch, int n, int tmax,
-                                                 int32_t* __restrict__ tile_first) {
-  const int lane = threadIdx.x;
-  long long run = 0;
-  for (int s0 = 0; s0 < batch; s0 += 64) {
-    const int s = s0 + lane;
-    long long v = 0;
-    if (s < batch) {
-      int lo, hi;
-      gtdb_span(scene_offsets, s, n, lo, hi);
-      v = ((long long)hi - lo + GT_T - 1) / GT_T;
-    }
-    long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (s < batch) tile_first[s] = (int32_t)min(run + inc - v, (long long)tmax);
-    run += __shfl(inc, 63);
-  }
-  if (lane == 0) tile_first[batch] = (int32_t)min(run, (long long)tmax);
-}
-
-// what a workgroup knows of its tile, the same in every thread
-struct GtTile {
-  int s;           // the scene
-  long long row0;  // the tile's first row
-  int hi;          // the scene's end: row i of the tile is live while i < hi
-  int b0, nbox;    // the scene's boxes [b0, b0 + nbox), nbox <= max_boxes
-};
-
-__device__ __forceinline__ bool gtdb_tile(const int32_t* __restrict__ tile_first, const int32_t* __restrict__ scene_offsets, int batch, int n,
-                                          const int32_t* __restrict__ box_offsets, int m, int max_boxes, GtTile& t) {
-  const int tile = blockIdx.x;
-  if (tile >= tile_first[batch]) return false;
-  t.s = aug_owner(tile_first, batch, tile);
-  int lo, b1;
-  gtdb_span(scene_offsets, t.s, n, lo, t.hi);
-  t.row0 = (long long)lo + (long long)(tile - tile_first[t.s]) * GT_T;
-  gtdb_span(box_offsets, t.s, m, t.b0, b1);
-  t.nbox = min(b1 - t.b0, max_boxes);
-  return true;
-}
-
-template <bool VEC4>
-__device__ __forceinline__ float4 gtdb_load(const float* __restrict__ p) {
-  if (VEC4) return *reinterpret_cast<const float4*>(p);
-  return make_float4(p[0], p[1], p[2], 0.f);
-}
 
 // One chunk of nb <= 64 boxes (rows `chunk` of the box array) against the workgroup's rows; every thread calls it (three barriers).
 // -> bit k: this thread's row is inside box k of the chunk.  s_wcnt[w][k] = rows of wave w inside box k (0 for k >= nb);
@@ -232,9 +175,6 @@ __global__ __launch_bounds__(GT_T) void gtdb_scatter(const float* __restrict__ p
     }
   }
 }
-
-// tiles aligned to scenes: every scene adds at most one partly filled tile
-inline long long gtdb_tmax(int n, int batch) { return ((long long)n + GT_T - 1) / GT_T + batch; }
 
 }  // namespace
 

@@ -13,7 +13,7 @@ crop=False: the reference cuts from the full scan), btc_cut_objects forms every 
 the reference's bookkeeping: names, paths, db_infos, by its own indexing.  The in-box test is database_sampler.points_in_boxes_mask bit
 for bit -- the test by which gt_sampling later removes scan rows under a pasted box.
 
-Not here: creating the info pickles (get_infos needs only numpy and can run anywhere), Waymo, the ABLATION variants."""
+Not here: creating the info pickles (btcdet_amd/kitti_infos.py), Waymo, the ABLATION variants."""
 import pathlib
 import pickle
 

@@ -10,8 +10,8 @@ What runs where: Calibration, scene() and the file reads are host work (O(boxes)
 points[fov_flag] over ~120 K rows per scan -- is btc_fov_crop (csrc/fov_crop.hip, include/btcdet_hip_frames.h), one stable compaction over
 the batch.  fov_crop_host() is the same step in the reference's numpy statements.
 
-Not here: creating the info pickles (get_infos, create_kitti_infos*), reading images (image shapes come from the infos), Waymo.  The
-ground-truth database is cut from these batches by btcdet_amd/gt_database.py.
+Not here: reading image pixels (image shapes come from the infos), Waymo.  The info pickles are made by btcdet_amd/kitti_infos.py and
+the ground-truth database is cut from these batches by btcdet_amd/gt_database.py.
 """
 import copy
 import os
@@ -157,19 +157,23 @@ def fov_crop(points, scene_offsets, calib, out=None, keep_idx=None):
 
 
 class KittiFrames(object):
-    """KittiFrames(root, split, info_path=None, fov_points_only=True): the frames of the reference's kitti_infos_<split>.pkl under `root`
-    (the scans, calibrations and planes under root/training, root/testing for the test split).  ImageSets/<split>.txt, when present,
-    is read into sample_id_list.  fov_points_only is the data configuration's FOV_POINTS_ONLY: without it nothing is cropped."""
+    """KittiFrames(root, split, info_path=None, fov_points_only=True, infos=None): the frames of the reference's kitti_infos_<split>.pkl
+    under `root` (the scans, calibrations and planes under root/training, root/testing for the test split), or of the list `infos`
+    when it is given.  ImageSets/<split>.txt, when present, is read into sample_id_list.  fov_points_only is the data
+    configuration's FOV_POINTS_ONLY: without it nothing is cropped."""
     NUM_POINT_FEATURES = 4
 
-    def __init__(self, root, split, info_path=None, fov_points_only=True):
+    def __init__(self, root, split, info_path=None, fov_points_only=True, infos=None):
         self.root, self.split, self.fov_points_only = pathlib.Path(root), split, bool(fov_points_only)
         self.split_dir = self.root / ("training" if split != "test" else "testing")
         ids = self.root / "ImageSets" / (split + ".txt")
         self.sample_id_list = [x.strip() for x in open(ids).readlines()] if ids.exists() else None
-        info_path = pathlib.Path(info_path) if info_path is not None else pathlib.Path("kitti_infos_%s.pkl" % split)
-        with open(self.root / info_path, "rb") as f:
-            self.infos = pickle.load(f)
+        if infos is not None:      # the list in memory (kitti_infos.KittiInfoBuilder: before any pickle exists); no file is opened
+            self.infos = infos
+        else:
+            info_path = pathlib.Path(info_path) if info_path is not None else pathlib.Path("kitti_infos_%s.pkl" % split)
+            with open(self.root / info_path, "rb") as f:
+                self.infos = pickle.load(f)
         self._calibs = {}
 
     def __len__(self):
