@@ -1,6 +1,6 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
-include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h, include/btcdet_hip_templates.h and
-include/btcdet_hip_infos.h).
+include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h, include/btcdet_hip_templates.h,
+include/btcdet_hip_infos.h and include/btcdet_hip_heads.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -253,6 +253,15 @@ _INFOS_SIGS = {
 
 INFOS_EXPORTED_SYMBOLS = tuple(_INFOS_SIGS.keys())
 
+# the entry points of the ninth public header, include/btcdet_hip_heads.h (same library, same rules; the h_ arguments are host arrays)
+_HEADS_SIGS = {
+    "btc_anchor_targets_ws_bytes": (sz, [ci, ci]),
+    "btc_anchor_targets": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "btc_decode_anchor_boxes": (ci, [vp, vp, vp, ci, ci, ci, cf, cf, vp, vp]),
+}
+
+HEADS_EXPORTED_SYMBOLS = tuple(_HEADS_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -264,7 +273,7 @@ def lib():
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
-                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items())):
+                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items()) + list(_HEADS_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

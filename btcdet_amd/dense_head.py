@@ -211,7 +211,21 @@ class AnchorHeadSingle(nn.Module):
         self._anchors = {}
         _, per_loc = make_anchors(point_cloud_range, model_cfg.ANCHOR_GENERATOR_CONFIG, grid_size, "cpu")
         self.num_anchors_per_location = sum(per_loc)
-        self.target_assigner = AxisAlignedTargetAssigner(model_cfg, class_names, self.box_coder, tgt.MATCH_HEIGHT)
+        # TARGET_ASSIGNER_CONFIG.DEVICE (opt-in): targets and boxes by csrc/anchor_targets.hip (anchor_targets.py) where the configuration
+        # is one it computes; otherwise, and without the key, the torch formulation above.  The decoded boxes then carry no gradient:
+        # nothing in the model differentiates through them (proposal_layer, their only consumer, runs under no_grad).
+        self.device_targets = False
+        if tgt.get("DEVICE", False):
+            from .anchor_targets import DeviceTargetAssigner
+            why = DeviceTargetAssigner.unsupported_reason(model_cfg, self.box_coder, tgt.MATCH_HEIGHT)
+            self.device_targets = why is None
+            if why is not None:
+                import logging
+                logging.getLogger(__name__).warning("TARGET_ASSIGNER_CONFIG.DEVICE is set but %s: the torch route is used", why)
+        if self.device_targets:
+            self.target_assigner = DeviceTargetAssigner(model_cfg, class_names, self.box_coder, tgt.MATCH_HEIGHT)
+        else:
+            self.target_assigner = AxisAlignedTargetAssigner(model_cfg, class_names, self.box_coder, tgt.MATCH_HEIGHT)
         self.forward_ret_dict = {}
         A = self.num_anchors_per_location
         self.conv_cls = nn.Conv2d(input_channels, A * num_class, kernel_size=1)
@@ -251,6 +265,12 @@ class AnchorHeadSingle(nn.Module):
         return a.view(1, -1, a.shape[-1]).repeat(batch_size, 1, 1)
 
     def generate_predicted_boxes(self, batch_size, cls_preds, box_preds, dir_cls_preds=None):
+        if self.device_targets:
+            from .anchor_targets import decode_boxes
+            flat = self.target_assigner.flat_anchors(self.anchors(cls_preds.device))
+            n = flat.shape[0]
+            dirs = dir_cls_preds.view(batch_size, n, -1) if dir_cls_preds is not None else None
+            return cls_preds.view(batch_size, n, -1).float(), decode_boxes(box_preds.view(batch_size, n, -1), flat, dirs, self.model_cfg)
         anchors = self._flat_anchors(cls_preds.device, batch_size)
         n = anchors.shape[1]
         scores = cls_preds.view(batch_size, n, -1).float()
