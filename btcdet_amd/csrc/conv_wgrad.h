@@ -2,6 +2,7 @@
 // every kernel family -- the four fp32-pipe families of conv_wgrad.hip, the bf16 matrix pipe (conv_wgrad_x.hip) and the narrow layers
 // (conv_wgrad_n.hip).  A family's plan function fills a WgradLaunch or refuses the shape; the launch is `L.fn(L, a)`, nothing is decided
 // after the plan: the instance, its grid, its LDS bytes and the slab count S the workspace is checked against are the ones launched.
+// (The device side has its counterpart in wgrad_tile.h: the staging, tile decode, slab stores, map ring and MFMA step loop the kernels share.)
 #pragma once
 #include "btc_common.h"
 

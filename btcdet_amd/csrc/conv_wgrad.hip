@@ -5,7 +5,12 @@
 // Every family writes S partial sums ("slabs") of K * Cin * Cout floats into the caller's workspace; wgrad_reduce adds them up in slab
 // order (deterministic).  A family's plan function fills the launch record of conv_wgrad.h (instance, grid, LDS bytes, S) or refuses the
 // shape; btc_conv_wgrad_ws_bytes asks the same plan functions (wgrad_max_slabs), and the launch is the record's: L.fn(L, a).
+//
+// The four kernels here are callers of wgrad_tile.h for what they share on the device: the register-batched staging of both operands,
+// the accumulator-tile decode and the slab stores, the map ring of conv_wgrad_rows_p, the LDS / LDS MFMA step loop and the block decode
+// of the offset-major pair.  What is written out in a kernel is what only that kernel has.
 #include "conv_wgrad.h"
+#include "wgrad_tile.h"
 
 namespace {
 
@@ -22,100 +27,41 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial(const float* __restric
   float* Ds = As + TM * WG_LDA;   // [TM][LDB]     dout rows, NT*16 channels
   int32_t* s_j = (int32_t*)(Ds + TM * LDB);  // [TM] (kept inside the one dynamic LDS array)
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x, split = blockIdx.y;
-  const int m0 = (blockIdx.z / n_cblk) * 64;
-  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int t_begin = split * tiles_per_split;
-  const int t_end = min(n_tiles, t_begin + tiles_per_split);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+  const WgOffsetBlock B = wg_offset_block<NT>(n_out, Cin, tiles_per_split, n_cblk);
+  const int k = B.k, m0 = B.m0, n0 = B.n0;
 
   f32x4 acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int kq = lane >> 4;
-  const bool wave_live = (m0 + wave * 16) < Cin;
 
-  for (int t = t_begin; t < t_end; ++t) {
+  for (int t = B.t_begin; t < B.t_end; ++t) {
     const int row0 = t * TM;
     int j = -1;
     if (tid < TM && row0 + tid < n_out) j = nbr[(size_t)(row0 + tid) * K + k];
     if (tid < TM) s_j[tid] = j;
     if (!__syncthreads_or(j >= 0)) continue;
     // all loads of a thread are issued before the first LDS store (one memory latency per tile)
+    auto arow = [&](int r) { return s_j[r]; };
+    auto drow = [&](int r) { return s_j[r] >= 0 ? row0 + r : -1; };
     if (((Cin | Cout) & 3) == 0) {
       float4 va[4], vd[NT];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-        int jj = s_j[r];
-        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c)
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-        float* d = As + r * WG_LDA + c;
-        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        float* d = Ds + r * LDB + c;
-        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
-      }
+      wg_stage_load<BF, 16>(va, feat, tid, arow, Cin, m0);
+      wg_stage_load<BF, NT * 4>(vd, dout, tid, drow, Cout, n0);
+      wg_stage_store<16>(va, As, WG_LDA, tid);
+      wg_stage_store<NT * 4>(vd, Ds, LDB, tid);
     } else {
       float va[16], vd[NT * 4];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        int e = i * 256 + tid, r = e >> 6, c = e & 63;
-        int jj = s_j[r];
-        va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld1<BF>(feat, (size_t)jj * Cin + m0 + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        vd[i] = (s_j[r] >= 0 && n0 + c < Cout) ? btc_ld1<BF>(dout, (size_t)(row0 + r) * Cout + n0 + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        int e = i * 256 + tid, r = e >> 6, c = e & 63;
-        As[r * WG_LDA + c] = va[i];
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        Ds[r * LDB + c] = vd[i];
-      }
+      wg_stage_load<BF, 64>(va, feat, tid, arow, Cin, m0);
+      wg_stage_load<BF, NT * 16>(vd, dout, tid, drow, Cout, n0);
+      wg_stage_store<64>(va, As, WG_LDA, tid);
+      wg_stage_store<NT * 16>(vd, Ds, LDB, tid);
     }
     __syncthreads();
-    if (wave_live) {
-#pragma unroll 4
-      for (int q = 0; q < TM / 4; ++q) {
-        float a = As[(q * 4 + kq) * WG_LDA + wave * 16 + (lane & 15)];
-        const float* bp = Ds + (q * 4 + kq) * LDB + (lane & 15);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[nt * 16], acc[nt], 0, 0, 0);
-      }
-    }
+    if (B.wave_live) wg_mfma_steps<NT>(acc, As + kq * WG_LDA + wave * 16 + (lane & 15), WG_LDA, Ds + kq * LDB + (lane & 15), LDB, TM / 4);
     __syncthreads();
   }
-  float* P = part + ((size_t)split * K + k) * Cin * Cout;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + nt * 16 + (lane & 15);
-    if (col >= Cout) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ci = m0 + wave * 16 + kq * 4 + r;
-      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
-    }
-  }
+  wg_store_slab_offset<NT>(part + ((size_t)B.split * K + k) * Cin * Cout, Cin, Cout, m0 + wave * 16 + kq * 4, n0 + (lane & 15), acc);
 }
 
 // conv_wgrad_partial for channel counts that are multiples of 4, with
@@ -139,19 +85,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_p(const float* __restr
   int32_t* s_dst = s_src + 2 * TM;             // [2][TM] output row of packed slot t
   int32_t* s_m = s_dst + 2 * TM;               // [2] live rows of the tile
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x, split = blockIdx.y;
-  const int m0 = (blockIdx.z / n_cblk) * 64;
-  const int n0 = (blockIdx.z % n_cblk) * (NT * 16);
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int t_begin = split * tiles_per_split;
-  const int t_end = min(n_tiles, t_begin + tiles_per_split);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
+  const WgOffsetBlock B = wg_offset_block<NT>(n_out, Cin, tiles_per_split, n_cblk);
+  const int k = B.k, m0 = B.m0, n0 = B.n0, t_begin = B.t_begin, t_end = B.t_end;
 
   f32x4 acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int kq = lane >> 4;
-  const bool wave_live = (m0 + wave * 16) < Cin;
 
   float4 va[4], vd[NT];
   auto load_j = [&](int t) {   // wave 0: map column entry of row `lane` of tile t
@@ -175,36 +115,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_p(const float* __restr
   };
   auto load_tile = [&](int b) {
     const int m4 = (s_m[b] + 3) & ~3;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-      const int jj = r < m4 ? s_src[b * TM + r] : -1;
-      va[i] = (jj >= 0 && m0 + c < Cin) ? btc_ld4<BF>(feat, (size_t)jj * Cin + m0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-      const int ro = r < m4 ? s_dst[b * TM + r] : -1;
-      vd[i] = (ro >= 0 && n0 + c < Cout) ? btc_ld4<BF>(dout, (size_t)ro * Cout + n0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    wg_stage_load<BF, 16>(va, feat, tid, [&](int r) { return r < m4 ? s_src[b * TM + r] : -1; }, Cin, m0);
+    wg_stage_load<BF, NT * 4>(vd, dout, tid, [&](int r) { return r < m4 ? s_dst[b * TM + r] : -1; }, Cout, n0);
   };
   auto store_tile = [&](int m4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = i * 256 + tid, r = e >> 4, c = (e & 15) * 4;
-      if (r < m4) {
-        float* d = As + r * WG_LDA + c;
-        d[0] = va[i].x; d[1] = va[i].y; d[2] = va[i].z; d[3] = va[i].w;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-      if (r < m4) {
-        float* d = Ds + r * LDB + c;
-        d[0] = vd[i].x; d[1] = vd[i].y; d[2] = vd[i].z; d[3] = vd[i].w;
-      }
-    }
+    wg_stage_store<16>(va, As, WG_LDA, tid, m4);
+    wg_stage_store<NT * 4>(vd, Ds, LDB, tid, m4);
   };
 
   // prologue: the first tile's column and loads, the second tile's column
@@ -224,31 +140,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_p(const float* __restr
     const int m4_next = (s_m[cur ^ 1] + 3) & ~3;
     if (m4_next) load_tile(cur ^ 1);   // in flight during the MFMAs below
     jn = load_j(t + 2);
-    if (m4 && wave_live) {
-      const int steps = m4 >> 2;
-      const float* ap = As + kq * WG_LDA + wave * 16 + (lane & 15);
-      const float* bp = Ds + kq * LDB + (lane & 15);
-#pragma unroll 4
-      for (int q = 0; q < steps; ++q) {
-        const float a = ap[q * 4 * WG_LDA];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[q * 4 * LDB + nt * 16], acc[nt], 0, 0, 0);
-      }
-    }
+    if (m4 && B.wave_live) wg_mfma_steps<NT>(acc, As + kq * WG_LDA + wave * 16 + (lane & 15), WG_LDA, Ds + kq * LDB + (lane & 15), LDB, m4 >> 2);
     __syncthreads();   // MFMAs of tile t done: the LDS tiles may be overwritten
     m4 = m4_next;
   }
-  float* P = part + ((size_t)split * K + k) * Cin * Cout;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = n0 + nt * 16 + (lane & 15);
-    if (col >= Cout) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ci = m0 + wave * 16 + kq * 4 + r;
-      if (ci < Cin) P[(size_t)ci * Cout + col] = acc[nt][r];
-    }
-  }
+  wg_store_slab_offset<NT>(part + ((size_t)B.split * K + k) * Cin * Cout, Cin, Cout, m0 + wave * 16 + kq * 4, n0 + (lane & 15), acc);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -300,33 +196,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows(const float* __restrict__
       if (v >= 0) s_kact[kk] = 1;
     }
     // dOut tile: all loads of a thread are issued before the first LDS store (one latency, not one per element)
+    auto drow = [&](int r) { return s_row[r]; };
     if ((Cout & 3) == 0) {
       float4 v[NT];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        const int gr = s_row[r];
-        v[i] = (gr >= 0 && c < Cout) ? btc_ld4<BF>(dout, (size_t)gr * Cout + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 4), c = (e % (NT * 4)) * 4;
-        float* d = Ds + r * LDB + c;
-        d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-      }
+      wg_stage_load<BF, NT * 4>(v, dout, tid, drow, Cout, 0);
+      wg_stage_store<NT * 4>(v, Ds, LDB, tid);
     } else {
       float v[NT * 4];
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        const int gr = s_row[r];
-        v[i] = (gr >= 0 && c < Cout) ? btc_ld1<BF>(dout, (size_t)gr * Cout + c) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < NT * 4; ++i) {
-        int e = i * 256 + tid, r = e / (NT * 16), c = e % (NT * 16);
-        Ds[r * LDB + c] = v[i];
-      }
+      wg_stage_load<BF, NT * 16>(v, dout, tid, drow, Cout, 0);
+      wg_stage_store<NT * 16>(v, Ds, LDB, tid);
     }
     __syncthreads();
 #pragma unroll
@@ -336,73 +214,36 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows(const float* __restrict__
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) any |= (k0 + kb < K) ? s_kact[k0 + kb] : 0;
       if (!any) continue;  // block-uniform
-      // gather KB input tiles; loads batched in registers as above
+      // gather KB input tiles (As row kb * TM + r: offset k0 + kb of tile row r); loads batched in registers as above
+      auto grow = [&](unsigned ra) {   // (unsigned: the divisions by TM are shifts)
+        const int r = ra % TM, kb = ra / TM;
+        return (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
+      };
       if ((Cin & 3) == 0) {
         float4 v[KB * MT];
-#pragma unroll
-        for (int i = 0; i < KB * MT; ++i) {
-          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
-          if (dbg & 8) j = -1;  // timing experiments only (BTC_TUNE_APPLY_DEBUG, tools/wgrad_bench.py): no gathers
-          v[i] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < KB * MT; ++i) {
-          int e = i * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-          float* d = As + (kb * TM + r) * LDA + c;
-          d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-        }
+        // dbg & 8: timing experiments only (BTC_TUNE_APPLY_DEBUG, tools/wgrad_bench.py): no gathers
+        wg_stage_load<BF, MT * 4>(v, feat, tid, [&](unsigned ra) { const int j = grow(ra); return (dbg & 8) ? -1 : j; }, Cin, 0);
+        wg_stage_store<MT * 4>(v, As, LDA, tid);
       } else {
         float v[KB * MT * 4];
-#pragma unroll
-        for (int i = 0; i < KB * MT * 4; ++i) {
-          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
-          int j = (k0 + kb < K) ? s_nbr[r * K + k0 + kb] : -1;
-          v[i] = (j >= 0 && c < Cin) ? btc_ld1<BF>(feat, (size_t)j * Cin + c) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < KB * MT * 4; ++i) {
-          int e = i * 256 + tid, c = e % (MT * 16), r = (e / (MT * 16)) % TM, kb = e / (MT * 16 * TM);
-          As[(kb * TM + r) * LDA + c] = v[i];
-        }
+        wg_stage_load<BF, MT * 16>(v, feat, tid, grow, Cin, 0);
+        wg_stage_store<MT * 16>(v, As, LDA, tid);
       }
       __syncthreads();
 #pragma unroll
       for (int q = 0; q < TPP; ++q) {
         if (dbg & 4) continue;       // timing experiments only: no MFMA phase
-        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt)
-        const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-        const float* ap = As + (size_t)kb * TM * LDA + mt * 16 + (lane & 15);
-        const float* bp = Ds + nt * 16 + (lane & 15);
-        f32x4 a4 = acc[p * TPP + q];
-#pragma unroll 4
-        for (int s = 0; s < TM / 4; ++s)
-          a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[(s * 4 + kq) * LDA], bp[(s * 4 + kq) * LDB], a4, 0, 0, 0);
-        acc[p * TPP + q] = a4;
+        const WgTile t = wg_tile<MT, NT>(q, wave);  // phase-local tile: (kb, mt, nt)
+        f32x4 a4[1] = {acc[p * TPP + q]};
+        wg_mfma_steps<1>(a4, As + (size_t)t.kb * TM * LDA + t.mt * 16 + (lane & 15) + kq * LDA, LDA, Ds + t.nt * 16 + (lane & 15) + kq * LDB, LDB, TM / 4);
+        acc[p * TPP + q] = a4[0];
       }
       __syncthreads();
     }
   }
-  // write this workgroup's slab: part[blockIdx.x][k][ci][co]
-  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
-#pragma unroll
-  for (int p = 0; p < PH; ++p)
-#pragma unroll
-    for (int q = 0; q < TPP; ++q) {
-      const int l = q * 4 + wave;
-      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-      const int k = kg0 + p * KB + kb;
-      const int co = nt * 16 + (lane & 15);
-      if (k >= K || co >= Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int ci = mt * 16 + kq * 4 + r;
-        if (ci < Cin) {
-          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
-          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];  // here ci indexes dOut channels, co feature channels
-        }
-      }
-    }
+  // write this workgroup's slab: part[blockIdx.x][k][ci][co] (swap: ci indexes dOut channels, co feature channels)
+  wg_store_slab_rows<MT, NT, KB, PH>(part + (size_t)blockIdx.x * K * Cin * Cout, K, Cin, Cout, kg0, swap,
+                                     [&](int p, int q, int r) { return acc[p * TPP + q][r]; });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -440,8 +281,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
   const int kg0 = blockIdx.y * NOFF;
-  const int n_tiles = (n_out + TM - 1) / TM;
-  const int nt_wg = ((int)blockIdx.x < n_tiles) ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;   // tiles of this workgroup
+  const int nt_wg = wg_tiles_of_workgroup((n_out + TM - 1) / TM);
   const int bcol = (wave % NT) * 16 + (lane & 15);   // this lane's column of the contiguous operand
 
   f32x4 acc[PH * TPP];
@@ -452,29 +292,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
   float4 gv[KB * MT];               // the gathered rows of an item, in flight
   float bcur[NS], bnext[NS];        // B fragments of the tile / of the next tile (in flight)
 
-  auto load_map = [&](int i) {      // tile i of this workgroup -> registers
-    const int row0 = (blockIdx.x + i * gridDim.x) * TM;
-    if (tid < TM) nrow = (row0 + tid < n_out) ? (order ? order[row0 + tid] : row0 + tid) : -1;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = u * 256 + tid, r = e / NOFF, o = e - r * NOFF;
-      int v = -1;
-      if (e < TM * NOFF && row0 + r < n_out && kg0 + o < K) {
-        const int gr = order ? order[row0 + r] : row0 + r;
-        v = nbr[(long long)gr * K + kg0 + o];
-      }
-      nv[u] = v;
-    }
-  };
-  auto store_map = [&](int i) {
-    int32_t* dn = s_nbr + (i % 3) * TM * NOFF;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = u * 256 + tid;
-      if (e < TM * NOFF) dn[e] = nv[u];
-    }
-    if (tid < TM) s_row[(i % 3) * TM + tid] = nrow;
-  };
+  auto load_map = [&](int i) { wg_load_map<TM, NOFF>(nv, nrow, i, nbr, order, n_out, K, kg0); };   // tile i of this workgroup -> registers
+  auto store_map = [&](int i) { wg_store_map<TM, NOFF, 3, 3>(nv, nrow, i, s_nbr, s_row); };
   auto load_b = [&](int i) {        // B fragments of tile i (its row ids are in LDS): row 4 s + kq, column bcol
     const int32_t* rows = s_row + (i % 3) * TM + kq;
 #pragma unroll
@@ -505,12 +324,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
       }
       return;
     }
-#pragma unroll
-    for (int u = 0; u < KB * MT; ++u) {
-      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-      const int j = mp[r * NOFF + kb];
-      gv[u] = (j >= 0 && c < Cin) ? btc_ld4<BF>(feat, (size_t)j * Cin + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    wg_stage_load<BF, MT * 4>(gv, feat, tid, [&](unsigned ra) { return mp[(ra % TM) * NOFF + ra / TM]; }, Cin, 0);   // As row kb * TM + r
   };
   auto store_g = [&](int buf) {
     float* A = As + buf * KB * TM * LDA;
@@ -530,12 +344,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
       }
       return;
     }
-#pragma unroll
-    for (int u = 0; u < KB * MT; ++u) {
-      const int e = u * 256 + tid, c = (e % (MT * 4)) * 4, r = (e / (MT * 4)) % TM, kb = e / (MT * 4 * TM);
-      float* d = A + (kb * TM + r) * LDA + c;
-      d[0] = gv[u].x; d[1] = gv[u].y; d[2] = gv[u].z; d[3] = gv[u].w;
-    }
+    wg_stage_store<MT * 4>(gv, A, LDA, tid);
   };
 
   if (nt_wg > 0) {
@@ -574,9 +383,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
       const float* A = As + buf * KB * TM * LDA;
 #pragma unroll
       for (int q = 0; q < TPP; ++q) {
-        const int l = q * 4 + wave;  // phase-local tile: (kb, mt, nt), nt == wave % NT
-        const int mt = (l / NT) % MT, kb = l / (NT * MT);
-        const float* ap = A + (size_t)kb * TM * LDA + mt * 16 + (lane & 15) + kq * LDA;
+        const WgTile t = wg_tile<MT, NT>(q, wave);  // phase-local tile: (kb, mt, nt), nt == wave % NT
+        const float* ap = A + (size_t)t.kb * TM * LDA + t.mt * 16 + (lane & 15) + kq * LDA;
         f32x4 a4 = acc[p * TPP + q];
 #pragma unroll
         for (int s2 = 0; s2 < NS; ++s2) a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[s2 * 4 * LDA], bcur[s2], a4, 0, 0, 0);
@@ -585,25 +393,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_p(const float* __restrict
       buf ^= 1;
     }
   }
-  float* P = part + (size_t)blockIdx.x * K * Cin * Cout;
-#pragma unroll
-  for (int p = 0; p < PH; ++p)
-#pragma unroll
-    for (int q = 0; q < TPP; ++q) {
-      const int l = q * 4 + wave;
-      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-      const int k = kg0 + p * KB + kb;
-      const int co = nt * 16 + (lane & 15);
-      if (k >= K || co >= Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int ci = mt * 16 + kq * 4 + r;
-        if (ci < Cin) {
-          if (!swap) P[((size_t)k * Cin + ci) * Cout + co] = acc[p * TPP + q][r];
-          else P[((size_t)k * Cout + co) * Cin + ci] = acc[p * TPP + q][r];
-        }
-      }
-    }
+  wg_store_slab_rows<MT, NT, KB, PH>(part + (size_t)blockIdx.x * K * Cin * Cout, K, Cin, Cout, kg0, swap,
+                                     [&](int p, int q, int r) { return acc[p * TPP + q][r]; });
 }
 
 // sum_s part[s][e] in slab order (deterministic): a chain of S dependent additions per element, bound by the round trips of its loads --

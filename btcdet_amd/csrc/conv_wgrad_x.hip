@@ -26,6 +26,7 @@
 
 #include "conv_tile.h"
 #include "conv_wgrad.h"
+#include "wgrad_tile.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -93,8 +94,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, t16 = lane & 15;
   const int kg0 = blockIdx.y * NOFF;
-  const int n_tiles = (n_rows + TMX - 1) / TMX;
-  const int nt_wg = ((int)blockIdx.x < n_tiles) ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
+  const int nt_wg = wg_tiles_of_workgroup((n_rows + TMX - 1) / TMX);
   const int bcol = cc0 + (wave % NT) * 16 + t16;       // this lane's column of the contiguous operand
   const bool bvalid = bcol < Cc_all;
   const int lane_off = (4 * g4 + (t16 >> 2)) * RS + (t16 & 3) * 8;   // transposing read: row 4 g + t / 4 of the block, 8-byte chunk t % 4
@@ -109,6 +109,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gsrc, 0, X_RECORDS, 0x00020000);
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)csrc, 0, X_RECORDS, 0x00020000);
   int nv[NV], nrow = -1;
+  // (wg_load_map / wg_store_map and wg_store_slab_rows of wgrad_tile.h, kept as this kernel's own bodies: through the shared ones
+  // conv_wgrad_x<2, 2, 2, 4, 0, 1> allocates 68 vector registers for 64 and loses a wave per SIMD, two registers per piece --
+  // profiles/wgrad_tile_resource_usage.txt)
   auto load_map = [&](int i) {
     const int row0 = (blockIdx.x + i * gridDim.x) * TMX;
     if (tid < TMX) nrow = (row0 + tid < n_rows) ? (order ? order[row0 + tid] : row0 + tid) : -1;
@@ -288,9 +291,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
     const char* A = As + buf * ITEM + lane_off;
     bf16x8 fh[2], fm[MODE ? 2 : 1], fl[MODE ? 2 : 1];
     auto read_step = [&](int t, int w) {
-      const int q = t >> 1, s2 = t & 1, l = q * 4 + wave;      // phase-local tile (kb, mt, nt), nt == wave % NT
-      const int mt = (l / NT) % MT, kb = l / (NT * MT);
-      const char* ap = A + kb * NPL * IMG + mt * 32 + 32 * s2 * RS;
+      const int q = t >> 1, s2 = t & 1;
+      const WgTile tl = wg_tile<MT, NT>(q, wave);              // phase-local tile (kb, mt, nt), nt == wave % NT
+      const char* ap = A + tl.kb * NPL * IMG + tl.mt * 32 + 32 * s2 * RS;
       fh[w] = frag_tr<RS>(ap);
       if (MODE) {
         fm[MODE ? w : 0] = frag_tr<RS>(ap + IMG);
@@ -384,19 +387,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_x(const void* __restrict__ gsr
   }
   // slab of this workgroup: part[blockIdx.x][k][ci][co]; D layout of 16x16: col = lane & 15 (contiguous operand's channel),
   // row = (lane >> 4) * 4 + reg (gathered operand's channel)
+  // slab of this workgroup: part[blockIdx.x][k][ci][co]; D layout of 16x16: col = lane & 15 (contiguous operand's channel),
+  // row = (lane >> 4) * 4 + reg (gathered operand's channel)
   float* P = part + (size_t)blockIdx.x * K * Cg_all * Cc_all;
 #pragma unroll
   for (int p = 0; p < PH; ++p)
 #pragma unroll
     for (int q = 0; q < TPP; ++q) {
-      const int l = q * 4 + wave;
-      const int nt = l % NT, mt = (l / NT) % MT, kb = l / (NT * MT);
-      const int k = kg0 + p * KB + kb;
-      const int co = cc0 + nt * 16 + t16;
+      const WgTile tl = wg_tile<MT, NT>(q, wave);
+      const int k = kg0 + p * KB + tl.kb;
+      const int co = cc0 + tl.nt * 16 + t16;
       if (k >= K || co >= Cc_all) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int ci = cg0 + mt * 16 + g4 * 4 + r;
+        const int ci = cg0 + tl.mt * 16 + g4 * 4 + r;
         float v = acc[0][p * TPP + q][r];
         if (MODE) v = v + (acc[NC > 1 ? 1 : 0][p * TPP + q][r] + acc[NC - 1][p * TPP + q][r]);
         if (!swap) P[((size_t)k * Cg_all + ci) * Cc_all + co] = v;

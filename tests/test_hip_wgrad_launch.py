@@ -34,14 +34,22 @@ LAUNCH_CASES = [
     ("x_full_ph", 16, 16, 27, 49152, ((NARROW, 1),)), ("x_full_ph", 32, 32, 27, 49152, ((NARROW, 1),)),
     ("x_swapped", 64, 32, 3, 16384, ((NARROW, 1),)),
     ("n_result_mirrored", 32, 5, 3, 2048, ()), ("n_result", 32, 5, 3, 2048, ()), ("n_input", 4, 16, 3, 2048, ()),
+    # paths of the fp32-pipe kernels that no row above reaches (csrc/wgrad_tile.h): two Cin blocks (the second with one live wave of
+    # four) x two Cout blocks of NT = 8 (the second 16 columns wide); scalar staging of both operands with the Cout bound inside a
+    # 16-column tile; conv_wgrad_rows with scalar / mixed staging (the plan takes it because Cg & 3); conv_wgrad_rows_p with
+    # bcol < Cout live; swap = 1 (2 * 4096 < 8200: 4096 walked rows, transposed slab store)
+    ("partial_p_blocks", 80, 144, 2, 129, FP32_PIPE), ("partial_blocks", 80, 144, 2, 129, FP32_PIPE + ((WGRAD_PIPE, 1),)),
+    ("partial_scalar", 34, 30, 3, 129, FP32_PIPE),
+    ("rows_scalar", 30, 30, 3, 4161, FP32_PIPE), ("rows_mixed", 30, 32, 3, 4096, FP32_PIPE), ("rows_p_edge", 32, 30, 3, 4161, FP32_PIPE),
+    ("rows_p_swapped", 64, 32, 3, 8200, FP32_PIPE), ("rows_swapped", 64, 32, 3, 8200, FP32_PIPE + ((WGRAD_PIPE, 1),)),
 ]
 
 
 def make_case(family, cin, cout, K, rows, bf16):
     """the layer of one LAUNCH_CASES row; n_result_mirrored: a map that is its own transpose with the offset index mirrored
     (nbr_in[j][k] == nbr_out[j][K - 1 - k], K = 3: a partial injection, a partial identity, the injection's inverse), as a submanifold
-    rulebook's is, handed in as nbr_in == nbr_out"""
-    kw = dict(n_src=rows // 8) if family == "x_swapped" else {}
+    rulebook's is, handed in as nbr_in == nbr_out; x_swapped / *_swapped: an input side of rows // 8 / rows // 2 - 4 rows"""
+    kw = dict(n_src=rows // 8) if family == "x_swapped" else (dict(n_src=rows // 2 - 4) if family.endswith("_swapped") else {})
     c = Case(cin * 1000 + cout * 10 + K + rows, rows, K, cin, cout, bf16=bf16, pairs_per_row=min(K, 4.0), **kw)
     if family == "n_result_mirrored":
         fwd = c.nbr_out[:, 0]
