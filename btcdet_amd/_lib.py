@@ -1,6 +1,6 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
 include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h, include/btcdet_hip_templates.h,
-include/btcdet_hip_infos.h and include/btcdet_hip_heads.h).
+include/btcdet_hip_infos.h, include/btcdet_hip_heads.h and include/btcdet_hip_anchor_loss.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -262,6 +262,15 @@ _HEADS_SIGS = {
 
 HEADS_EXPORTED_SYMBOLS = tuple(_HEADS_SIGS.keys())
 
+# the entry points of the tenth public header, include/btcdet_hip_anchor_loss.h: the loss over what btc_anchor_targets leaves on the device
+_ANCHOR_LOSS_SIGS = {
+    "btc_anchor_loss_ws_bytes": (sz, [ci, ci]),
+    "btc_anchor_loss_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp, vp, sz, vp]),
+    "btc_anchor_loss_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp]),
+}
+
+ANCHOR_LOSS_EXPORTED_SYMBOLS = tuple(_ANCHOR_LOSS_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -273,7 +282,8 @@ def lib():
                 f"or `make -C btcdet_amd/csrc` (there is no CPU fallback for the hot path)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
-                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items()) + list(_HEADS_SIGS.items())):
+                                  list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items()) + list(_HEADS_SIGS.items()) +
+                                  list(_ANCHOR_LOSS_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -226,6 +226,17 @@ class AnchorHeadSingle(nn.Module):
             self.target_assigner = DeviceTargetAssigner(model_cfg, class_names, self.box_coder, tgt.MATCH_HEIGHT)
         else:
             self.target_assigner = AxisAlignedTargetAssigner(model_cfg, class_names, self.box_coder, tgt.MATCH_HEIGHT)
+        # LOSS_CONFIG.DEVICE (opt-in): get_loss by csrc/anchor_loss.hip (anchor_loss.py), one launch each way, where the configuration is
+        # one it computes and the call's tensors are float32 on the GPU; otherwise, and without the key, the torch formulation below.
+        self.device_loss = False
+        if model_cfg.LOSS_CONFIG.get("DEVICE", False):
+            from . import anchor_loss
+            why = anchor_loss.unsupported_reason(model_cfg, self.box_coder, num_class)
+            self.device_loss = why is None
+            if why is not None:
+                import logging
+                logging.getLogger(__name__).warning("LOSS_CONFIG.DEVICE is set but %s: the torch route is used", why)
+        self._flat = {}
         self.forward_ret_dict = {}
         A = self.num_anchors_per_location
         self.conv_cls = nn.Conv2d(input_channels, A * num_class, kernel_size=1)
@@ -282,7 +293,33 @@ class AnchorHeadSingle(nn.Module):
             boxes[..., 6] = limit_period(boxes[..., 6] - off, lim, period) + off + period * which.to(boxes.dtype)
         return scores, boxes
 
+    def _device_get_loss(self):
+        """get_loss through btc_anchor_loss_fwd / _bwd, or None when this call's tensors are not the kernels' (the torch route then)"""
+        from . import anchor_loss as al
+        from .occ_head import _lazy_scalars
+        f = self.forward_ret_dict
+        cls_preds, labels, reg_t, dirs = f["cls_preds"], f["box_cls_labels"], f["box_reg_targets"], f.get("dir_cls_preds")
+        if not al.usable(cls_preds, f["box_preds"], dirs, labels, reg_t):
+            return None
+        B, A = int(labels.shape[0]), int(labels.shape[1])
+        if self.device_targets:
+            flat = self.target_assigner.flat_anchors(self.anchors(cls_preds.device))
+        else:
+            key = str(cls_preds.device)
+            if key not in self._flat:
+                self._flat[key] = torch.cat(self.anchors(cls_preds.device), dim=-3).reshape(-1, 7).float().contiguous()
+            flat = self._flat[key]
+        loss, parts = al.anchor_loss(cls_preds.view(B, A, -1), f["box_preds"].view(B, A, -1), dirs.view(B, A, -1) if dirs is not None else None, labels,
+                                     reg_t, flat, self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS, self.model_cfg.get("DIR_OFFSET", 0.0))
+        vals = _lazy_scalars(parts, 4)
+        keys = ["rpn_loss_cls", "rpn_loss_loc"] + (["rpn_loss_dir"] if dirs is not None else []) + ["rpn_loss"]
+        return loss, {k: vals[{"rpn_loss_cls": 0, "rpn_loss_loc": 1, "rpn_loss_dir": 2, "rpn_loss": 3}[k]] for k in keys}
+
     def get_loss(self):
+        if self.device_loss:
+            fused = self._device_get_loss()
+            if fused is not None:
+                return fused
         f, w = self.forward_ret_dict, self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
         cls_preds, labels = f["cls_preds"], f["box_cls_labels"]
         B = int(cls_preds.shape[0])
