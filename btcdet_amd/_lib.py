@@ -1,6 +1,6 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
 include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h, include/btcdet_hip_templates.h,
-include/btcdet_hip_infos.h, include/btcdet_hip_heads.h and include/btcdet_hip_anchor_loss.h).
+include/btcdet_hip_infos.h, include/btcdet_hip_heads.h, include/btcdet_hip_anchor_loss.h and include/btcdet_hip_roi_targets.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -272,6 +272,22 @@ _ANCHOR_LOSS_SIGS = {
 ANCHOR_LOSS_EXPORTED_SYMBOLS = tuple(_ANCHOR_LOSS_SIGS.keys())
 
 
+class BtcRoiTargetsConfig(ctypes.Structure):
+    """struct BtcRoiTargetsConfig of include/btcdet_hip_roi_targets.h (host memory)"""
+    _fields_ = [("R", ctypes.c_int32), ("fg_quota", ctypes.c_int32), ("by_class", ctypes.c_int32), ("score_type", ctypes.c_int32),
+                ("reg_fg", ctypes.c_float), ("cls_fg", ctypes.c_float), ("cls_bg", ctypes.c_float), ("cls_bg_lo", ctypes.c_float),
+                ("fg_thresh", ctypes.c_float), ("cls_span", ctypes.c_float), ("hard_bg_ratio", ctypes.c_double)]
+
+
+# the entry points of the eleventh public header, include/btcdet_hip_roi_targets.h: the ROI head's targets in one launch (cfg: a host struct)
+_ROI_TARGETS_SIGS = {
+    "btc_roi_targets_ws_bytes": (sz, [ci, ci]),
+    "btc_roi_targets": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(BtcRoiTargetsConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+ROI_TARGETS_EXPORTED_SYMBOLS = tuple(_ROI_TARGETS_SIGS.keys())
+
+
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
     global _lib
@@ -283,7 +299,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
                                   list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items()) + list(_HEADS_SIGS.items()) +
-                                  list(_ANCHOR_LOSS_SIGS.items())):
+                                  list(_ANCHOR_LOSS_SIGS.items()) + list(_ROI_TARGETS_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

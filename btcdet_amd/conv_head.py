@@ -323,6 +323,20 @@ class ConvHead(nn.Module):
         """RoIHeadTemplate.assign_targets (roi_head_template.py:102-134): ROI_PER_IMAGE sampled rois per scene with their matched boxes
         in the roi's frame (btcdet_amd/roi_targets.py: resident, no read-back)"""
         from .roi_targets import ProposalTargetLayer, canonical_targets
+        # TARGET_CONFIG.DEVICE (opt-in): the targets by csrc/roi_targets.hip (roi_targets_device.py), one launch, where the configuration is
+        # one it computes and the call's tensors are float32 / int64 on the GPU with 7-wide rois; otherwise, and without the key, the torch route
+        if getattr(self, "device_targets", None) is None:
+            self.device_targets = False
+            if self.model_cfg.TARGET_CONFIG.get("DEVICE", False):
+                from . import roi_targets_device
+                why = roi_targets_device.unsupported_reason(self.model_cfg.TARGET_CONFIG)
+                if why is None:
+                    self.device_targets = roi_targets_device.DeviceProposalTargets(self.model_cfg.TARGET_CONFIG)
+                else:
+                    import logging
+                    logging.getLogger(__name__).warning("ROI_HEAD.TARGET_CONFIG.DEVICE is set but %s: the torch route is used", why)
+        if self.device_targets and self.device_targets.usable(batch_dict):
+            return self.device_targets(batch_dict, sampled_inds)
         if getattr(self, "proposal_target_layer", None) is None:
             self.proposal_target_layer = ProposalTargetLayer(self.model_cfg.TARGET_CONFIG)
         return canonical_targets(self.proposal_target_layer(batch_dict, sampled_inds))

@@ -37,8 +37,9 @@ def _kth_of(mask):
     return torch.sort((~mask).to(torch.uint8), stable=True)[1]
 
 
-def sample_rois(max_overlaps, cfg, generator=None):
-    """proposal_target_layer.py:117-197 for one scene, on the device: -> ROI_PER_IMAGE sampled roi indices (foreground slots first)."""
+def sample_rois(max_overlaps, cfg, generator=None, uniforms=None):
+    """proposal_target_layer.py:117-197 for one scene, on the device: -> ROI_PER_IMAGE sampled roi indices (foreground slots first).
+    uniforms (4, max(ROI_PER_IMAGE, N)): used instead of drawing (roi_targets_device.py samples from the same block: equal draws)"""
     R = int(cfg.ROI_PER_IMAGE)
     fg_quota = int(round(float(cfg.FG_RATIO) * R))
     ov, dev = max_overlaps, max_overlaps.device
@@ -47,7 +48,7 @@ def sample_rois(max_overlaps, cfg, generator=None):
     hard = (ov < cfg.REG_FG_THRESH) & (ov >= cfg.CLS_BG_THRESH_LO)
     n_fg, n_easy, n_hard = fg.sum(), easy.sum(), hard.sum()
     n_bg = n_easy + n_hard
-    u = torch.rand((4, max(R, ov.shape[0])), device=dev, generator=generator)
+    u = torch.rand((4, max(R, ov.shape[0])), device=dev, generator=generator) if uniforms is None else uniforms
     # foreground candidates in random order (a random permutation's prefix = sampling without replacement)
     fg_order = torch.sort(torch.where(fg, u[0, :ov.shape[0]], u.new_full((), 2.0)))[1]
     hard_list, easy_list = _kth_of(hard), _kth_of(easy)
@@ -79,8 +80,9 @@ class ProposalTargetLayer(nn.Module):
         return self._gen
 
     @torch.no_grad()
-    def forward(self, batch_dict, sampled_inds=None):
-        """sampled_inds (B, ROI_PER_IMAGE): use these roi indices instead of drawing (tests: the reference's own draw)"""
+    def forward(self, batch_dict, sampled_inds=None, uniforms=None):
+        """sampled_inds (B, ROI_PER_IMAGE): use these roi indices instead of drawing (tests: the reference's own draw);
+        uniforms (B, 4, max(ROI_PER_IMAGE, N)): scene b samples from uniforms[b] instead of drawing"""
         cfg = self.roi_sampler_cfg
         rois, scores, labels, gts = batch_dict["rois"], batch_dict["roi_scores"], batch_dict["roi_labels"], batch_dict["gt_boxes"]
         B = batch_dict["batch_size"]
@@ -90,7 +92,12 @@ class ProposalTargetLayer(nn.Module):
                 ov, assign = match_rois(rois[b], labels[b], gts[b])
             else:
                 ov, assign = iou3d_nms.boxes_iou3d_gpu(rois[b][:, 0:7].contiguous(), gts[b][:, 0:7].contiguous()).max(dim=1)
-            sel = sample_rois(ov, cfg, self._generator(rois.device) if rois.is_cuda else None) if sampled_inds is None else sampled_inds[b]
+            if sampled_inds is not None:
+                sel = sampled_inds[b]
+            elif uniforms is not None:
+                sel = sample_rois(ov, cfg, uniforms=uniforms[b])
+            else:
+                sel = sample_rois(ov, cfg, self._generator(rois.device) if rois.is_cuda else None)
             out["rois"].append(rois[b][sel])
             out["gt_of_rois"].append(gts[b][assign[sel]])
             out["gt_iou_of_rois"].append(ov[sel])
