@@ -84,7 +84,7 @@ __global__ __launch_bounds__(AT_T) void at_prepare(const float* __restrict__ gt,
     if (s != 0.0f) last = j;   // j ascends per thread
     top[(size_t)b * M + j] = 0u;
   }
-  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o));
+  last = btc_wave_all_max(last);
   if ((threadIdx.x & 63) == 0) s_last[threadIdx.x >> 6] = last;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(AT_T) void at_top(const float* __restrict__ anchors
       if (cfg < 0) continue;   // the same in every thread
       unsigned bits = cfg == mine ? at_bits(at_iou(fa, s_foot[k])) : 0u;
       if (__ballot(bits != 0u) == 0ull) continue;   // the same in every lane of the wave
-      for (int o = 32; o > 0; o >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, o));
+      bits = btc_wave_all_max(bits);
       if ((threadIdx.x & 63) == 0) atomicMax(s_top + k, bits);
     }
     __syncthreads();

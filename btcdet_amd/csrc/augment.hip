@@ -76,19 +76,7 @@ __global__ __launch_bounds__(64) void aug_offsets(const unsigned char* __restric
                                                   int32_t* __restrict__ obj_prefix, int32_t* __restrict__ out_offsets) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x == batch + 1) {
-    int run = 0;
-    for (int j0 = 0; j0 < n_objects; j0 += 64) {
-      const int j = j0 + lane;
-      const int v = j < n_objects ? max(obj_rows[j], 0) : 0;
-      int inc = v;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-      }
-      if (j < n_objects) obj_prefix[j] = run + inc - v;
-      run += __shfl(inc, 63);
-    }
-    if (lane == 0) obj_prefix[n_objects] = run;
+    btc_wave_offsets_of_counts(obj_rows, n_objects, obj_prefix);
     return;
   }
   const int s = blockIdx.x;
@@ -97,8 +85,7 @@ __global__ __launch_bounds__(64) void aug_offsets(const unsigned char* __restric
   if (n_objects > 0) {
     const int j1 = min(max(obj_offsets[s], 0), n_objects);
     for (int j = lane; j < j1; j += 64) pasted += max(obj_rows[j], 0);
-    for (int o = 32; o > 0; o >>= 1) pasted += __shfl_down(pasted, o);
-    pasted = __shfl(pasted, 0);
+    pasted = btc_wave_all_sum(pasted);
   }
   if (lane == 0) {
     kept_off[s] = kept;

@@ -56,6 +56,7 @@ void btc_set_error(const char* fmt, ...);
 #error "the fence-free last-arriver protocol (btc_ticket_take) is derived for gfx950's sc1 write-through stores only"
 #endif
 #if defined(__HIPCC__)
+#include "wave_ops.h"   // wave and workgroup reductions and scans
 template <class T>
 __device__ __forceinline__ void btc_st_agent(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <class T>

@@ -8,8 +8,10 @@
 //
 // The helpers take a `bool keep` and do not know the predicate: the caller decides once and stores a flag byte per row (augment, fov
 // crop), or decides again in every stage (range mask: four comparisons are cheaper than a byte written and read).
+// The boundary stage's wave sum is wave_ops.h's (as are the scans of aug_offsets' object block, gtdb_offsets and tsel_offsets behind
+// the same batches); the rank stage is a ballot and a popcount and stays here.
 #pragma once
-#include "btc_common.h"
+#include "btc_common.h"   // (wave_ops.h comes with it)
 
 constexpr int BTC_COMPACT_T = 256;   // rows (threads) per workgroup of the count and scatter stages
 
@@ -62,8 +64,7 @@ static __device__ __forceinline__ int btc_compact_boundary(int s, const int32_t*
   const int blk = pos / BTC_COMPACT_T;
   int cnt = 0;
   for (int j = blk * BTC_COMPACT_T + (int)threadIdx.x; j < pos; j += 64) cnt += kept(j);
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-  return block_prefix[blk] + __shfl(cnt, 0);
+  return block_prefix[blk] + btc_wave_all_sum(cnt);
 }
 
 // one row of ld floats; VEC4: ld == 4 and both ends 16-byte aligned, one load and one store

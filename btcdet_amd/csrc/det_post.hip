@@ -191,8 +191,7 @@ struct FinArgs {
 };
 
 __device__ __forceinline__ float block_max(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+  v = btc_wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
   __syncthreads();
   v = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));

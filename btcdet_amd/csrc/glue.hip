@@ -117,8 +117,7 @@ __global__ __launch_bounds__(256) void sumsq2_fwd_k(const void* __restrict__ a, 
   acc_a = sumsq(a, na, std::integral_constant<bool, BFA>());
   acc_b = sumsq(b, nb, std::integral_constant<bool, BFB>());
   double acc = acc_a * ka + acc_b * kb;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  acc = btc_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -133,8 +132,7 @@ __global__ __launch_bounds__(256) void sumsq2_fwd_k(const void* __restrict__ a, 
   btc_ticket_acquire();
   double s = 0.0;
   for (int g = threadIdx.x; g < (int)gridDim.x; g += 256) s += btc_ld_agent(partial + g);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  s = btc_wave_sum(s);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
   __syncthreads();

@@ -82,7 +82,6 @@ __global__ __launch_bounds__(GT_T) void gtdb_count(const float* __restrict__ pts
 __global__ __launch_bounds__(64) void gtdb_box_scan(const int32_t* __restrict__ box_offsets, int batch, int m, int max_boxes,
                                                     const int32_t* __restrict__ tile_first, int32_t* __restrict__ cnt,
                                                     int32_t* __restrict__ obj_total) {
-  const int lane = threadIdx.x;
   const int j = blockIdx.x;
   const int s = aug_owner(box_offsets, batch, j);
   int b0, b1;
@@ -91,38 +90,16 @@ __global__ __launch_bounds__(64) void gtdb_box_scan(const int32_t* __restrict__ 
   int run = 0;
   if (j >= b0 && j < b1 && k < max_boxes) {
     const int t0 = tile_first[s], t1 = tile_first[s + 1];
-    for (int tb = t0; tb < t1; tb += 64) {
-      const int t = tb + lane;
-      int32_t* c = cnt + (size_t)t * max_boxes + k;
-      const int v = t < t1 ? *c : 0;
-      int inc = v;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-      }
-      if (t < t1) *c = run + inc - v;
-      run += __shfl(inc, 63);
-    }
+    int32_t* c = cnt + (size_t)t0 * max_boxes + k;   // box k's cell of the scene's first tile; the next tile's is max_boxes further on
+    run = btc_wave_excl_scan_chunks<int>(t1 - t0, [=](int t) { return c[(size_t)t * max_boxes]; },
+                                         [=](int t, int prefix) { c[(size_t)t * max_boxes] = prefix; });
   }
-  if (lane == 0) obj_total[j] = run;
+  if (threadIdx.x == 0) obj_total[j] = run;
 }
 
-// obj_offsets[j] = rows of the objects in front of object j, obj_offsets[m] = all (the pattern of aug_offsets' last block)
+// obj_offsets[j] = rows of the objects in front of object j, obj_offsets[m] = all
 __global__ __launch_bounds__(64) void gtdb_offsets(const int32_t* __restrict__ obj_total, int m, int32_t* __restrict__ obj_offsets) {
-  const int lane = threadIdx.x;
-  int run = 0;
-  for (int j0 = 0; j0 < m; j0 += 64) {
-    const int j = j0 + lane;
-    const int v = j < m ? max(obj_total[j], 0) : 0;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (j < m) obj_offsets[j] = run + inc - v;
-    run += __shfl(inc, 63);
-  }
-  if (lane == 0) obj_offsets[m] = run;
+  btc_wave_offsets_of_counts(obj_total, m, obj_offsets);
 }
 
 template <bool VEC4>

@@ -126,17 +126,6 @@ __device__ __forceinline__ int cv_insert(unsigned* tab, unsigned mask, unsigned 
   return 0;
 }
 
-// the sum of `v` over the workgroup, in every thread; every thread calls it
-__device__ __forceinline__ int cv_block_sum(int v, int* s_red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  __syncthreads();   // s_red's previous values have been read
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int sum = 0;
-  for (int w = 0; w < CV_WAVES; ++w) sum += s_red[w];
-  return sum;
-}
-
 __global__ __launch_bounds__(CV_T) void coverage_cells(const float* __restrict__ tmpl_rows, int T, const float* __restrict__ obj_rows, int R, int ld,
                                                        const int32_t* __restrict__ jobs, const double* __restrict__ pose_all, int max_rows,
                                                        unsigned cap_max, unsigned* __restrict__ ws_tab, int32_t* __restrict__ cells,
@@ -144,7 +133,6 @@ __global__ __launch_bounds__(CV_T) void coverage_cells(const float* __restrict__
   __shared__ unsigned s_tab[BTC_COVERAGE_LDS_KEYS];
   __shared__ double s_ext[CV_WAVES][6];
   __shared__ double s_mn[3], s_n[3];
-  __shared__ int s_red[CV_WAVES];
   const int j = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t0 = jobs[j * 4 + 0], tn = jobs[j * 4 + 1], o0 = jobs[j * 4 + 2], on = jobs[j * 4 + 3];
@@ -171,10 +159,8 @@ __global__ __launch_bounds__(CV_T) void coverage_cells(const float* __restrict__
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[k] = fmin(lo[k], __shfl_down(lo[k], o));
-      hi[k] = fmax(hi[k], __shfl_down(hi[k], o));
-    }
+    lo[k] = btc_wave_reduce(lo[k], [](double a, double b) { return fmin(a, b); });
+    hi[k] = btc_wave_reduce(hi[k], [](double a, double b) { return fmax(a, b); });
   }
   if (lane == 0) {
 #pragma unroll
@@ -215,7 +201,7 @@ __global__ __launch_bounds__(CV_T) void coverage_cells(const float* __restrict__
     }
     fresh += cv_insert(tab, mask, key);
   }
-  const int unique_bm = cv_block_sum(fresh, s_red);
+  const int unique_bm = btc_block_sum<CV_WAVES>(fresh);
 
   // pass 3: the object's kept cells, in the cleared table
   __syncthreads();   // every insert of pass 2 has been made
@@ -235,7 +221,7 @@ __global__ __launch_bounds__(CV_T) void coverage_cells(const float* __restrict__
     }
     if (keep) fresh += cv_insert(tab, mask, key);
   }
-  const int unique_obj = cv_block_sum(fresh, s_red);
+  const int unique_obj = btc_block_sum<CV_WAVES>(fresh);
   if (threadIdx.x == 0) cells[j * 2 + 0] = unique_obj, cells[j * 2 + 1] = unique_bm, status[j] = BTC_COVERAGE_OK;
 }
 

@@ -58,8 +58,7 @@ __global__ __launch_bounds__(256) void occ_loss_fwd(const float* __restrict__ lo
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+    acc[q] = btc_wave_sum(acc[q]);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6][q] = acc[q];
   }
   __syncthreads();

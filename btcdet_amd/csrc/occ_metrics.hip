@@ -94,9 +94,7 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_cells(CellArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const unsigned v = btc_wave_sum(c[k]);
     if ((tid & 63) == 0) s_part[tid >> 6][k] = v;
   }
   __syncthreads();
@@ -196,9 +194,7 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_points(PointArgs a) {
   }
 #pragma unroll
   for (int t = 0; t < OCC_N_THRESH; ++t) {
-    unsigned v = cnt[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const unsigned v = btc_wave_sum(cnt[t]);
     if ((tid & 63) == 0 && v) atomicAdd(&s_cnt[t], v);
   }
   u64 nb = 0;

@@ -193,8 +193,7 @@ __global__ __launch_bounds__(256) void occ_ray_count(const uint8_t* __restrict__
   const uint8_t* r = smap + (size_t)ray * P.snx;
   int c = 0;
   for (int x = lane; x < P.snx; x += 64) c += r[x];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  c = btc_wave_sum(c);
   if (lane == 0) ray_cnt[ray] = c;
 }
 

@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void adam_sqnorm(GradPtrs ptrs, const int32_t*
       acc += (double)v * v;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) acc += __shfl_down(acc, d, 64);
+  acc = btc_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[c] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);

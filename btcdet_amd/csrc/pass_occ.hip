@@ -30,36 +30,13 @@ struct PovGeom {
 constexpr float kPiF = 3.14159274101257324f;
 
 // ------------------------------------------------------------------ exact top-k per scene
-template <int T>
-__device__ __forceinline__ int block_excl_scan_i(int v, int* s_w, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int w = 0; w < T / 64; ++w) { int t = s_w[w]; s_w[w] = run; run += t; }
-    s_w[T / 64] = run;
-  }
-  __syncthreads();
-  int r = incl - v + s_w[wave];
-  *total = s_w[T / 64];
-  __syncthreads();
-  return r;
-}
-
 // find, scanning bins from the TOP, the bin where the running count reaches `want`; returns bin, writes the count above it
-__device__ __forceinline__ int find_bin(const int* __restrict__ hist /*2048 LDS*/, int want, int* s_w, int* s_res /*[2]*/) {
+__device__ __forceinline__ int find_bin(const int* __restrict__ hist /*2048 LDS*/, int want, int* s_res /*[2]*/) {
   // thread t owns bins 2047-2t and 2046-2t (descending order), exclusive scan of their sums
   const int t = threadIdx.x;
   int h0 = hist[2047 - 2 * t], h1 = hist[2046 - 2 * t];
   int tot;
-  int ex = block_excl_scan_i<1024>(h0 + h1, s_w, &tot);
+  int ex = btc_block_excl_scan<1024 / 64>(h0 + h1, &tot);
   if (ex < want && want <= ex + h0) { s_res[0] = 2047 - 2 * t; s_res[1] = ex; }
   else if (ex + h0 < want && want <= ex + h0 + h1) { s_res[0] = 2046 - 2 * t; s_res[1] = ex + h0; }
   __syncthreads();
@@ -69,9 +46,7 @@ __device__ __forceinline__ int find_bin(const int* __restrict__ hist /*2048 LDS*
 __global__ __launch_bounds__(1024) void pov_select(const float* __restrict__ probs, const uint8_t* __restrict__ use, PovGeom G, float thresh,
                                                    int32_t* __restrict__ sel, int32_t* __restrict__ counts) {
   __shared__ int s_hist[2048];
-  __shared__ int s_w[1024 / 64 + 1];
   __shared__ int s_res[2];
-  __shared__ int s_cnt;
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* p = probs + (size_t)b * G.ncell;
   const unsigned* pk = reinterpret_cast<const unsigned*>(p);
@@ -82,13 +57,7 @@ __global__ __launch_bounds__(1024) void pov_select(const float* __restrict__ pro
   // number of candidates
   int c = 0;
   for (int i = tid; i < G.ncell; i += 1024) c += (p[i] > thresh);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((tid & 63) == 0) atomicAdd(&s_cnt, c);
-  __syncthreads();
-  const int n_cand = s_cnt;
+  const int n_cand = btc_block_sum<1024 / 64>(c);
   unsigned T = 0;      // selection threshold key: keep key > T, plus the first `need_eq` keys == T
   int need_eq = 0;
   const bool all = n_cand <= G.max_k;
@@ -106,7 +75,7 @@ __global__ __launch_bounds__(1024) void pov_select(const float* __restrict__ pro
         if (p[i] > thresh && (k & pmask) == prefix) atomicAdd(&s_hist[(k >> shifts[pass]) & ((1u << widths[pass]) - 1u)], 1);
       }
       __syncthreads();
-      find_bin(s_hist, want, s_w, s_res);
+      find_bin(s_hist, want, s_res);
       const int bin = s_res[0], above = s_res[1];
       want -= above;
       prefix |= (unsigned)bin << shifts[pass];
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(1024) void pov_select(const float* __restrict__ pro
       ne += e[j];
     }
     int tot_e, tot_f;
-    const int ex_e = block_excl_scan_i<1024>(ne, s_w, &tot_e) + eq_seen;
+    const int ex_e = btc_block_excl_scan<1024 / 64>(ne, &tot_e) + eq_seen;
     // ties: the j-th equal key of this thread has global tie rank ex_e + (#equal before it in the thread)
     int te = 0, take[4], nt = 0;
 #pragma unroll
@@ -141,7 +110,7 @@ __global__ __launch_bounds__(1024) void pov_select(const float* __restrict__ pro
       te += e[j];
       nt += take[j];
     }
-    const int ex_t = block_excl_scan_i<1024>(nt, s_w, &tot_f) + base;
+    const int ex_t = btc_block_excl_scan<1024 / 64>(nt, &tot_f) + base;
     int pos = ex_t;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -161,14 +130,14 @@ constexpr int POV_CHUNK = 16384;  // cells per workgroup = 4 iterations of the 1
 struct PovSel { unsigned prefix, pmask; int want, all; };
 
 // prefix of the max_k-th largest key after `npass` radix passes (the passes' histograms are complete in ghist_b)
-__device__ PovSel pov_resolve(const int* __restrict__ ghist_b, int npass, int max_k, int* s_hist, int* s_w, int* s_res) {
+__device__ PovSel pov_resolve(const int* __restrict__ ghist_b, int npass, int max_k, int* s_hist, int* s_res) {
   PovSel r{0u, 0u, max_k, 0};
   const int shifts[3] = {21, 10, 0};
   const int widths[3] = {11, 11, 10};
   for (int q = 0; q < npass; ++q) {
     for (int i = threadIdx.x; i < 2048; i += 1024) s_hist[i] = ghist_b[q * 2048 + i];
     __syncthreads();
-    const int tot = find_bin(s_hist, r.want, s_w, s_res);
+    const int tot = find_bin(s_hist, r.want, s_res);
     if (q == 0 && tot <= max_k) { r.all = 1; return r; }  // fewer candidates than the cap: keep them all
     const int bin = s_res[0], above = s_res[1];
     r.want -= above;
@@ -183,12 +152,11 @@ template <int PASS>
 __global__ __launch_bounds__(1024) void pov_hist(const float* __restrict__ probs, const uint8_t* __restrict__ use, PovGeom G, float thresh,
                                                  int* __restrict__ ghist) {
   __shared__ int s_hist[2048];
-  __shared__ int s_w[1024 / 64 + 1];
   __shared__ int s_res[2];
   const int b = blockIdx.y, tid = threadIdx.x;
   if (use && !use[b]) return;
   int* gh = ghist + (size_t)b * 3 * 2048;
-  PovSel r = pov_resolve(gh, PASS, G.max_k, s_hist, s_w, s_res);
+  PovSel r = pov_resolve(gh, PASS, G.max_k, s_hist, s_res);
   if (r.all) return;
   for (int i = tid; i < 2048; i += 1024) s_hist[i] = 0;
   __syncthreads();
@@ -211,12 +179,11 @@ __global__ __launch_bounds__(1024) void pov_chunk_count(const float* __restrict_
                                                         const int* __restrict__ ghist, int n_chunk, int32_t* __restrict__ cc,
                                                         int32_t* __restrict__ state) {
   __shared__ int s_hist[2048];
-  __shared__ int s_w[1024 / 64 + 1];
   __shared__ int s_res[2];
   __shared__ int s_nf, s_ne;
   const int b = blockIdx.y, tid = threadIdx.x;
   if (use && !use[b]) return;
-  PovSel r = pov_resolve(ghist + (size_t)b * 3 * 2048, 3, G.max_k, s_hist, s_w, s_res);
+  PovSel r = pov_resolve(ghist + (size_t)b * 3 * 2048, 3, G.max_k, s_hist, s_res);
   const unsigned T = r.all ? 0u : r.prefix;
   if (tid == 0) { s_nf = 0; s_ne = 0; }
   __syncthreads();
@@ -230,8 +197,7 @@ __global__ __launch_bounds__(1024) void pov_chunk_count(const float* __restrict_
     nf += cand && (r.all || k > T);
     ne += cand && !r.all && k == T;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { nf += __shfl_down(nf, o, 64); ne += __shfl_down(ne, o, 64); }
+  nf = btc_wave_sum(nf), ne = btc_wave_sum(ne);
   if ((tid & 63) == 0) { atomicAdd(&s_nf, nf); atomicAdd(&s_ne, ne); }
   __syncthreads();
   if (tid == 0) {
@@ -245,7 +211,6 @@ __global__ __launch_bounds__(1024) void pov_chunk_count(const float* __restrict_
 __global__ __launch_bounds__(1024) void pov_chunk_scan(const uint8_t* __restrict__ use, int n_chunk, const int32_t* __restrict__ cc,
                                                        const int32_t* __restrict__ state, int32_t* __restrict__ co,
                                                        int32_t* __restrict__ counts) {
-  __shared__ int s_w[1024 / 64 + 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (use && !use[b]) {
     if (tid == 0) counts[b] = 0;
@@ -257,10 +222,10 @@ __global__ __launch_bounds__(1024) void pov_chunk_scan(const uint8_t* __restrict
     const int c = c0 + tid;
     const int nf = c < n_chunk ? cc[((size_t)b * n_chunk + c) * 2 + 0] : 0, ne = c < n_chunk ? cc[((size_t)b * n_chunk + c) * 2 + 1] : 0;
     int tot_e, tot_t;
-    const int ex_e = block_excl_scan_i<1024>(ne, s_w, &tot_e) + base_e;
+    const int ex_e = btc_block_excl_scan<1024 / 64>(ne, &tot_e) + base_e;
     int take_e = need_eq - ex_e;
     take_e = take_e < 0 ? 0 : (take_e > ne ? ne : take_e);
-    const int ex_t = block_excl_scan_i<1024>(nf + take_e, s_w, &tot_t) + base_t;
+    const int ex_t = btc_block_excl_scan<1024 / 64>(nf + take_e, &tot_t) + base_t;
     if (c < n_chunk) {
       co[((size_t)b * n_chunk + c) * 2 + 0] = ex_t;
       co[((size_t)b * n_chunk + c) * 2 + 1] = ex_e;
@@ -275,7 +240,6 @@ __global__ __launch_bounds__(1024) void pov_chunk_scan(const uint8_t* __restrict
 __global__ __launch_bounds__(1024) void pov_chunk_write(const float* __restrict__ probs, const uint8_t* __restrict__ use, PovGeom G, float thresh,
                                                         int n_chunk, const int32_t* __restrict__ co, const int32_t* __restrict__ state,
                                                         int32_t* __restrict__ sel) {
-  __shared__ int s_w[1024 / 64 + 1];
   const int b = blockIdx.y, tid = threadIdx.x;
   if (use && !use[b]) return;
   const unsigned T = (unsigned)state[b * 4 + 0];
@@ -299,7 +263,7 @@ __global__ __launch_bounds__(1024) void pov_chunk_write(const float* __restrict_
       ne += e[j];
     }
     int tot_e, tot_f;
-    const int ex_e = block_excl_scan_i<1024>(ne, s_w, &tot_e) + eq_seen;
+    const int ex_e = btc_block_excl_scan<1024 / 64>(ne, &tot_e) + eq_seen;
     int te = 0, take[4], nt = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -307,7 +271,7 @@ __global__ __launch_bounds__(1024) void pov_chunk_write(const float* __restrict_
       te += e[j];
       nt += take[j];
     }
-    const int ex_t = block_excl_scan_i<1024>(nt, s_w, &tot_f) + base;
+    const int ex_t = btc_block_excl_scan<1024 / 64>(nt, &tot_f) + base;
     int pos = ex_t;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -405,8 +369,7 @@ __global__ __launch_bounds__(256) void pov_info(const int32_t* __restrict__ cnt,
                                                 int B, int32_t* __restrict__ info /* [m, pmax, counts...] */) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   int v = (r < *d_m) ? cnt[r] : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
+  v = btc_wave_max(v);
   if ((threadIdx.x & 63) == 0 && v > 0) atomicMax(&info[1], v);
   if (r == 0) {
     info[0] = *d_m;

@@ -56,8 +56,7 @@ __global__ __launch_bounds__(256) void rv_pmax(const int32_t* __restrict__ cnt, 
                                                int32_t* __restrict__ d_pmax) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   int v = (r < *d_m) ? cnt[r] : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
+  v = btc_wave_max(v);
   if ((threadIdx.x & 63) == 0 && v > 0) atomicMax(d_pmax, v);
 }
 

@@ -73,36 +73,13 @@ __device__ __forceinline__ float rt_mod_two_pi(float x) {
   return m;
 }
 
-// exclusive prefix of v over the workgroup's threads in thread order; *total = the sum.  Called by every thread.
-__device__ __forceinline__ int rt_exscan(int v, int* s_wave /* RT_WAVES + 1 */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();   // (the previous call's readers of s_wave have left)
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int base = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < RT_WAVES; ++w) {
-    const int t = s_wave[w];
-    if (w < wave) base += t;
-    sum += t;
-  }
-  *total = sum;
-  return base + inc - v;
-}
-
 // members of `flag` in ascending index, then the non-members in ascending index (thread t owns rois t * RT_PER ..)
-__device__ __forceinline__ int rt_list(const bool* flag /* RT_PER */, int N, unsigned short* list, int* s_wave) {
+__device__ __forceinline__ int rt_list(const bool* flag /* RT_PER */, int N, unsigned short* list) {
   int mine = 0;
 #pragma unroll
   for (int k = 0; k < RT_PER; ++k) mine += flag[k] ? 1 : 0;
   int total;
-  int rank = rt_exscan(mine, s_wave, &total);
+  int rank = btc_block_excl_scan<RT_WAVES>(mine, &total);
 #pragma unroll
   for (int k = 0; k < RT_PER; ++k) {
     const int i = threadIdx.x * RT_PER + k;
@@ -129,7 +106,6 @@ __global__ __launch_bounds__(RT_T) void roi_targets_kernel(const float* __restri
   __shared__ int s_asg[RT_MAX];
   __shared__ float s_key[RT_MAX];
   __shared__ unsigned short s_fg[RT_MAX], s_hard[RT_MAX], s_easy[RT_MAX];
-  __shared__ int s_wave[RT_WAVES + 1];
   const int b = blockIdx.x / P.tiles, tile = blockIdx.x % P.tiles;
   const int N = P.N, G = P.G, R = P.c.R;
 
@@ -186,12 +162,12 @@ __global__ __launch_bounds__(RT_T) void roi_targets_kernel(const float* __restri
       hard[k] = i < N && ov < P.c.reg_fg && ov >= P.c.cls_bg_lo;
       if (i < N) s_key[i] = fg[k] ? u0[i] : 2.0f;
     }
-    n_hard = rt_list(hard, N, s_hard, s_wave);
-    n_easy = rt_list(easy, N, s_easy, s_wave);
+    n_hard = rt_list(hard, N, s_hard);
+    n_easy = rt_list(easy, N, s_easy);
     int mine = 0;
 #pragma unroll
     for (int k = 0; k < RT_PER; ++k) mine += fg[k] ? 1 : 0;
-    rt_exscan(mine, s_wave, &n_fg);
+    n_fg = btc_block_sum<RT_WAVES>(mine);
     __syncthreads();   // s_key is complete
     // the rank of a foreground member by (key, index): a background key of 2 is above every uniform.  Members are dealt out to the
     // threads one by one here (the scans above own RT_PER neighbours per thread, which would leave 3 of 4 threads idle at N = 256)

@@ -86,13 +86,7 @@ __global__ __launch_bounds__(ORDER_T) void order_local(OrderJobs jobs, int32_t* 
       loc[q] = e < ORDER_BINS * ORDER_W ? s_cnt[e] : 0;
       sum += loc[q];
     }
-    int incl = sum;   // inclusive wave scan of the per-lane sums
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    int run = incl - sum;
+    int run = btc_wave_incl_scan(sum) - sum;   // the sums of the lanes in front of mine
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
       const int e = lane * PER + q;

@@ -441,38 +441,10 @@ __global__ __launch_bounds__(RB_T) void rb_mark_multi(const int4* __restrict__ i
   }
 }
 
-__device__ __forceinline__ int rb_wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// exclusive prefix of v over the workgroup's threads: wave scan, then the totals of the waves in front of mine through s_wave (RB_T / 64
-// words, which the caller must not have in use); *total = the workgroup's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = rb_wave_incl_scan(v);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < RB_T / 64; ++w) {
-    base += (w < wave) ? s_wave[w] : 0;
-    tot += s_wave[w];
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
 // one thread per 32-byte block: chunk-relative block prefixes; the LAST workgroup to arrive turns the chunk sums into
 // chunk prefixes and publishes the level's row count (device, and a pinned host word when given)
 __device__ __forceinline__ void scan_chunk(const Level& L, int32_t* __restrict__ chunk_sums, int32_t* __restrict__ counter, int nchunks,
                                            int32_t* __restrict__ d_total, int chunk) {
-  __shared__ int s_wave[RB_T / 64 + 1];
   __shared__ int s_last;
   const long long blk = (long long)chunk * RB_CHUNK + threadIdx.x;
   int cnt = 0;
@@ -482,7 +454,7 @@ __device__ __forceinline__ void scan_chunk(const Level& L, int32_t* __restrict__
     cnt = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
   }
   int tot;
-  const int excl = block_excl_scan(cnt, s_wave, &tot);
+  const int excl = btc_block_excl_scan<RB_T / 64>(cnt, &tot);
   if (blk < L.nblk) L.bprefix[blk] = excl;
   if (threadIdx.x == 0) {
     // (device-scope store + drained queue instead of a release fence -- which writes back the XCD L2 once per workgroup, bn_fuse.h)
@@ -497,9 +469,8 @@ __device__ __forceinline__ void scan_chunk(const Level& L, int32_t* __restrict__
   for (int c0 = 0; c0 < nchunks; c0 += RB_T) {
     const int c = c0 + threadIdx.x;
     const int v = c < nchunks ? btc_ld_agent(&chunk_sums[c]) : 0;
-    __syncthreads();   // the round before has read s_wave
     int t2;
-    const int excl = block_excl_scan(v, s_wave, &t2);
+    const int excl = btc_block_excl_scan<RB_T / 64>(v, &t2);
     if (c < nchunks) L.cprefix[c] = carry + excl;
     carry += t2;
   }

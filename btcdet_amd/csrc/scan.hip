@@ -74,69 +74,25 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// exclusive scan across the block of per-thread values; returns exclusive prefix, total in *block_total
-template <int THREADS>
-__device__ __forceinline__ int block_excl_scan(int v, int* s_wave /* THREADS/64 + 1 */, int* block_total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = wave_incl_scan(v);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-      int t = s_wave[w];
-      s_wave[w] = run;
-      run += t;
-    }
-    s_wave[THREADS / 64] = run;
-  }
-  __syncthreads();
-  int r = incl - v + s_wave[wave];
-  *block_total = s_wave[THREADS / 64];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void scan_block_reduce(const int32_t* __restrict__ in, long long n,
                                                                   int32_t* __restrict__ block_sums) {
-  __shared__ int s_wave[SCAN_THREADS / 64];
   long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int sum = 0;
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j)
     if (base + j < n) sum += in[base + j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) t += s_wave[w];
-    block_sums[blockIdx.x] = t;
-  }
+  const int t = btc_block_sum<SCAN_THREADS / 64>(sum);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(1024) void scan_block_sums(int32_t* __restrict__ block_sums, int nblocks,
                                                         int32_t* __restrict__ total) {
-  __shared__ int s_wave[1024 / 64 + 1];
   int carry = 0;
   for (int base = 0; base < nblocks; base += 1024) {
     int i = base + threadIdx.x;
     int v = i < nblocks ? block_sums[i] : 0;
     int tot;
-    int ex = block_excl_scan<1024>(v, s_wave, &tot);
+    int ex = btc_block_excl_scan<1024 / 64>(v, &tot);
     if (i < nblocks) block_sums[i] = ex + carry;
     carry += tot;
   }
@@ -145,7 +101,6 @@ __global__ __launch_bounds__(1024) void scan_block_sums(int32_t* __restrict__ bl
 
 __global__ __launch_bounds__(SCAN_THREADS) void scan_final(const int32_t* __restrict__ in, int32_t* __restrict__ out,
                                                            long long n, const int32_t* __restrict__ block_sums) {
-  __shared__ int s_wave[SCAN_THREADS / 64 + 1];
   long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int v[SCAN_ITEMS];
   int sum = 0;
@@ -155,7 +110,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_final(const int32_t* __rest
     sum += v[j];
   }
   int tot;
-  int ex = block_excl_scan<SCAN_THREADS>(sum, s_wave, &tot) + block_sums[blockIdx.x];
+  int ex = btc_block_excl_scan<SCAN_THREADS / 64>(sum, &tot) + block_sums[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j) {
     if (base + j < n) out[base + j] = ex;
@@ -169,17 +124,9 @@ constexpr int SCAN_FUSE_BLOCKS = 4096;
 
 __global__ __launch_bounds__(SCAN_THREADS) void scan_final_fused(const int32_t* __restrict__ in, int32_t* __restrict__ out, long long n,
                                                                  const int32_t* __restrict__ block_sums, int32_t* __restrict__ total) {
-  __shared__ int s_wave[SCAN_THREADS / 64 + 1];
-  __shared__ int s_off[SCAN_THREADS / 64];
   int part = 0;
   for (int j = threadIdx.x; j < (int)blockIdx.x; j += SCAN_THREADS) part += block_sums[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, 64);
-  if ((threadIdx.x & 63) == 0) s_off[threadIdx.x >> 6] = part;
-  __syncthreads();
-  int offset = 0;
-#pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) offset += s_off[w];
+  const int offset = btc_block_sum<SCAN_THREADS / 64>(part);
   long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int v[SCAN_ITEMS];
   int sum = 0;
@@ -189,7 +136,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_final_fused(const int32_t* 
     sum += v[j];
   }
   int tot;
-  int ex = block_excl_scan<SCAN_THREADS>(sum, s_wave, &tot) + offset;
+  int ex = btc_block_excl_scan<SCAN_THREADS / 64>(sum, &tot) + offset;
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j) {
     if (base + j < n) out[base + j] = ex;
@@ -204,7 +151,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_final_fused(const int32_t* 
 // bytes_to_bits packs 32 bytes into a bitmap word and leaves the per-block popcount sums for the scan.
 __global__ __launch_bounds__(SCAN_THREADS) void bytes_to_bits(const uint4* __restrict__ bytemap, long long nwords,
                                                               unsigned* __restrict__ bitmap, int32_t* __restrict__ block_sums) {
-  __shared__ int s_wave[SCAN_THREADS / 64];
   const long long wbase = (long long)blockIdx.x * SCAN_TILE;
   int sum = 0;
 #pragma unroll
@@ -220,22 +166,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void bytes_to_bits(const uint4* __res
       sum += __popc(bits);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) t += s_wave[w];
-    block_sums[blockIdx.x] = t;
-  }
+  const int t = btc_block_sum<SCAN_THREADS / 64>(sum);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = t;
 }
 
 // prefix[w] = number of set bits in words [0, w), w in [0, nwords] (block_sums already scanned)
 __global__ __launch_bounds__(SCAN_THREADS) void bitmap_prefix(const unsigned* __restrict__ bitmap, long long nwords,
                                                               const int32_t* __restrict__ block_sums, int32_t* __restrict__ prefix) {
-  __shared__ int s_wave[SCAN_THREADS / 64 + 1];
   long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int v[SCAN_ITEMS];
   int sum = 0;
@@ -245,7 +182,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void bitmap_prefix(const unsigned* __
     sum += v[j];
   }
   int tot;
-  int ex = block_excl_scan<SCAN_THREADS>(sum, s_wave, &tot) + block_sums[blockIdx.x];
+  int ex = btc_block_excl_scan<SCAN_THREADS / 64>(sum, &tot) + block_sums[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j) {
     if (base + j <= nwords) prefix[base + j] = ex;

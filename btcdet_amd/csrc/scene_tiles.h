@@ -1,8 +1,9 @@
 // Tiles of 256 rows aligned to scenes, stated once (gt_database.hip: btc_cut_objects, kitti_infos.hip: btc_count_in_boxes): tile t of
 // scene s covers rows scene_offsets[s] + 256 t .., so a tile meets the boxes (and the calibration) of one scene only and the number of
 // tiles is at most ceil(n / 256) + batch, a bound the host knows.  Every index formed from a device array is clamped before use.
+// gtdb_tiles is one wave over the scenes: wave_ops.h's chunked exclusive scan in 64 bits, clamped to tmax as it stores.
 #pragma once
-#include "compact.h"   // aug_owner, BTC_COMPACT_T
+#include "compact.h"   // aug_owner, BTC_COMPACT_T; btc_wave_excl_scan_chunks through btc_common.h
 
 namespace {
 
@@ -17,25 +18,15 @@ __device__ __forceinline__ void gtdb_span(const int32_t* __restrict__ offs, int 
 // tile_first[s] = tiles in front of scene s, tile_first[batch] = all of them; never above tmax
 __global__ __launch_bounds__(64) void gtdb_tiles(const int32_t* __restrict__ scene_offsets, int batch, int n, int tmax,
                                                  int32_t* __restrict__ tile_first) {
-  const int lane = threadIdx.x;
-  long long run = 0;
-  for (int s0 = 0; s0 < batch; s0 += 64) {
-    const int s = s0 + lane;
-    long long v = 0;
-    if (s < batch) {
-      int lo, hi;
-      gtdb_span(scene_offsets, s, n, lo, hi);
-      v = ((long long)hi - lo + GT_T - 1) / GT_T;
-    }
-    long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (s < batch) tile_first[s] = (int32_t)min(run + inc - v, (long long)tmax);
-    run += __shfl(inc, 63);
-  }
-  if (lane == 0) tile_first[batch] = (int32_t)min(run, (long long)tmax);
+  const long long all = btc_wave_excl_scan_chunks<long long>(
+      batch,
+      [=](int s) {
+        int lo, hi;
+        gtdb_span(scene_offsets, s, n, lo, hi);
+        return ((long long)hi - lo + GT_T - 1) / GT_T;
+      },
+      [=](int s, long long prefix) { tile_first[s] = (int32_t)min(prefix, (long long)tmax); });
+  if (threadIdx.x == 0) tile_first[batch] = (int32_t)min(all, (long long)tmax);
 }
 
 // what a workgroup knows of its tile, the same in every thread

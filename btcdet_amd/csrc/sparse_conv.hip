@@ -271,8 +271,7 @@ __global__ __launch_bounds__(WS_WAVES * 64) void conv_apply_ws(const float* __re
         nb[e] = v;
         if (v >= 0) kmask |= 1ull << kk;
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) kmask |= __shfl_xor(kmask, o, 64);
+      kmask = btc_wave_all_or(kmask);
     }
     __builtin_amdgcn_wave_barrier();
     f32x4 acc[NT];

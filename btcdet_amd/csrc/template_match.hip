@@ -160,7 +160,7 @@ __global__ __launch_bounds__(TM_T) void tm_match(const float* __restrict__ pts, 
       for (int j = 0; j < TM_QR; ++j)
         if (live[j]) run = fmaxf(run, m[j]);
     }
-    for (int o = 32; o > 0; o >>= 1) run = fmaxf(run, __shfl_xor(run, o));
+    run = btc_wave_allreduce(run, [](float a, float b) { return fmaxf(a, b); });
     if ((tid & 63) == 0) s_wmax[tid >> 6] = run;
     __syncthreads();   // s_wmax and every bit of s_bits
     if (tid == 0) {
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(TM_T) void tsel_pick(const float* __restrict__ pts,
     s_alive[k] = on;
     alive += on;
   }
-  for (int o = 32; o > 0; o >>= 1) alive += __shfl_xor(alive, o);
+  alive = btc_wave_all_sum(alive);
   if (lane == 0) s_red[wave] = alive;
   for (int w = tid; w < W; w += TM_T) s_aug[w] = i >= 0 ? own_occ[(size_t)i * W + w] : 0u;
   for (int r = tid; r < max_bm; r += TM_T) chosen[(size_t)g * max_bm + r] = -1;
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(TM_T) void tsel_pick(const float* __restrict__ pts,
         s_aug[w] = v;
         bits += __popc(v);
       }
-      for (int o = 32; o > 0; o >>= 1) bits += __shfl_xor(bits, o);
+      bits = btc_wave_all_sum(bits);
       if (lane == 0) s_red[wave] = bits;
       __syncthreads();   // s_red, s_aug, s_set_*, and this round's flag bytes
       aug_num = 0;
@@ -300,22 +300,9 @@ __global__ __launch_bounds__(TM_T) void tsel_pick(const float* __restrict__ pts,
   if (tid == 0) total[g] = set_rows;
 }
 
-// tmpl_offsets[g] = rows of the templates in front of template g, tmpl_offsets[G] = all (the pattern of gtdb_offsets)
+// tmpl_offsets[g] = rows of the templates in front of template g, tmpl_offsets[G] = all
 __global__ __launch_bounds__(64) void tsel_offsets(const int32_t* __restrict__ total, int G, int32_t* __restrict__ tmpl_offsets) {
-  const int lane = threadIdx.x;
-  int run = 0;
-  for (int j0 = 0; j0 < G; j0 += 64) {
-    const int j = j0 + lane;
-    const int v = j < G ? max(total[j], 0) : 0;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (j < G) tmpl_offsets[j] = run + inc - v;
-    run += __shfl(inc, 63);
-  }
-  if (lane == 0) tmpl_offsets[G] = run;
+  btc_wave_offsets_of_counts(total, G, tmpl_offsets);
 }
 
 __global__ __launch_bounds__(TM_T) void tsel_write(const float* __restrict__ pts, int n, const int32_t* __restrict__ seg, int M,

@@ -6,6 +6,7 @@ host, and the device arithmetic is spelled out unfused.
   whole path   the three scenes as one batch and as three batches of one, both queue orders, both removal widths: points,
                pre_rot_points, rot_z, scene_offsets, every host key, two special sets per scene (44 and 45 rows)
   edge shapes  hand-made plans through btc_augment_batch; expectation = database_sampler.points_in_boxes_mask + the host functions
+               (scene sizes around a workgroup, boundaries inside one, 63 / 64 / 65 / 129 pasted objects around the 64 of a wave)
   sync=False   under torch.cuda.set_sync_debug_mode("error")
   chained      DataProcessor.forward_raw_batch on apply's output == on the uploaded host-chain result, same shuffle_idx"""
 import numpy as np
@@ -249,6 +250,23 @@ def test_uneven_batch_with_a_scene_boundary_inside_a_workgroup():
     d2, h2 = _ops(flip=False, order="rs", angle=-0.7)
     check_case(scans, boxes, objects, bank, [d0, d1, d2], [h0, h1, h2], ld)
     check_case(scans, boxes, objects, bank, [d0, d1, d2], [h0, h1, h2], ld, with_pre=False)
+
+
+@pytest.mark.parametrize("n_objects", [63, 64, 65, 129])
+def test_pasted_objects_around_the_chunks_of_the_object_scan(n_objects):
+    """one wave scans the objects' row counts 64 at a time, and one wave per scene boundary sums the rows pasted in front of it 64
+    objects at a time: objects of 1 - 3 rows, all but four in the first scene, none in the second, the last four in the third"""
+    rng = np.random.default_rng(300 + n_objects)
+    ld = 4
+    bank = _bank(rng, ld)
+    scans = [_scene(rng, 70, ld), _scene(rng, 30, ld), _scene(rng, 5, ld)]
+    boxes = [_boxes(rng, 1), np.zeros((0, 7), np.float32), _boxes(rng, 1)]
+    rows = rng.integers(1, 4, n_objects)
+    objs = [(int(rng.integers(0, bank.shape[0] - 3)), int(r), tuple(rng.uniform((0, -20, -2), (40, 20, 1))), float(rng.integers(0, 3)) / 8) for r in rows]
+    objects = [objs[:-4], [], objs[-4:]]
+    d0, h0 = _ops()
+    d2, h2 = _ops(flip=False, order="rs", angle=-0.7)
+    check_case(scans, boxes, objects, bank, [d0, [], d2], [h0, [], h2], ld)
 
 
 def test_every_row_removed_and_empty_programs():

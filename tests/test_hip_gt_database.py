@@ -5,7 +5,8 @@ create_groundtruth_database wrote (tests/golden/gt_database.npz).  Everything is
 The shapes are the smallest at which the kernel can go wrong: scenes of 0 / 1 / 255 / 256 / 257 rows (one tile is 256 rows, tiles are
 aligned to scenes), several scenes inside one 256-row span, a scene without boxes between two with boxes, 0 / 1 / 64 / 65 boxes in a
 scene (64 are staged per pass), ld 3 / 4 / 5 and a base pointer off 16 bytes (the scalar path), an empty object, an object that takes
-every row, a row in two objects, out_capacity below the total, max_boxes at and below the maximum, and the exact case on the faces."""
+every row, a row in two objects, out_capacity below the total, max_boxes at and below the maximum, and the exact case on the faces.
+The one-wave scans take 64 values at a time: 63 / 129 objects in all, a scene of 65 tiles, 65 scenes."""
 import copy
 import pickle
 
@@ -115,13 +116,31 @@ def test_row_lengths_and_an_unaligned_base(ld, misalign):
     check_case(pts, offs, boxes, misalign=misalign, want_src=False)
 
 
-@pytest.mark.parametrize("nbox", [0, 1, 64, 65])
+@pytest.mark.parametrize("nbox", [0, 1, 60, 64, 65, 126])
 def test_boxes_in_a_scene_around_a_staging_pass(nbox):
-    """the scene of 600 rows (three tiles) owns nbox boxes; a scene in front of it and one behind own 2 and 1"""
+    """the scene of 600 rows (three tiles) owns nbox boxes; a scene in front of it and one behind own 2 and 1.  nbox = 60 and 126 make
+    m = 63 and 129 objects: obj_offsets is a scan by one wave, 64 objects at a time, and 129 carries its running sum over two edges"""
     pts, offs, boxes = make_batch((100, 600, 50), (2, nbox, 1), seed=2)
     want_offs = check_case(pts, offs, boxes)
     if nbox:
         assert int(want_offs[2 + nbox] - want_offs[2]) > 100, "the boxes of the middle scene hold rows"
+
+
+def test_a_scene_of_65_tiles():
+    """a box's rows are counted per tile and scanned over its scene's tiles by one wave, 64 tiles at a time: 64 * 256 + 1 rows are 65
+    tiles, the last of which starts from the sum of the first 64"""
+    pts, offs, boxes = make_batch((64 * 256 + 1,), (2,), seed=9)
+    pts[-1, :3] = boxes[0][0, :3]                                   # the one row of tile 64 sits at the first box's centre
+    want_offs = check_case(pts, offs, boxes)
+    assert (np.diff(want_offs) > 256).all(), "each box holds rows of several tiles"
+
+
+def test_more_scenes_than_one_chunk_of_the_tile_scan():
+    """tile_first is an exclusive scan over the scenes by one wave, 64 at a time: 65 scenes of 3 rows, every fourth with a box"""
+    pts, offs, boxes = make_batch([3] * 65, [1 if b % 4 == 0 else 0 for b in range(65)], seed=10)
+    pts[-1, :3] = boxes[64][0, :3]                                  # the last scene's box (behind the chunk edge) holds a row
+    want_offs = check_case(pts, offs, boxes)
+    assert int(np.diff(want_offs)[-1]) > 0 and (np.diff(want_offs) > 0).sum() > 4
 
 
 def test_several_scenes_inside_one_span_and_a_scene_without_boxes_between():

@@ -7,7 +7,8 @@ The shapes are the smallest at which the compaction can go wrong: one scene of 0
 is 64 rows, a workgroup 256), a scene boundary inside a wave, inside a workgroup and exactly on a multiple of 256, empty scenes first /
 middle / last, everything / nothing kept, rows exactly on the four limits and one float32 ulp outside them, NaN coordinates, payload bits
 that are no numbers, ld 2 / 3 / 4 / 5 with a second array of ld_b 3 / 4 or none, with and without keep_idx, and each of the four bases in
-turn 4 bytes off a 16-byte boundary (the scalar path)."""
+turn 4 bytes off a 16-byte boundary (the scalar path), and one scene of 256 * 2048 + 257 rows (more workgroup counts than one tile of
+the device scan)."""
 import numpy as np
 import pytest
 import torch
@@ -116,6 +117,15 @@ def check_case(pts, offsets, pre=None, lim=LIM, **kw):
 def test_one_scene_at_wave_and_workgroup_edges(n):
     want_offs = check_case(*batch([n], seed=n))
     assert n < 63 or 0 < want_offs[-1] < n, "some rows kept, some dropped"
+
+
+def test_more_workgroup_counts_than_one_scan_tile():
+    """256 * 2048 + 257 rows are 2050 workgroups of the count stage and the device scan takes 2048 counts per workgroup: two scan
+    workgroups, the second of which starts from the sum of the first's counts"""
+    n = 256 * 2048 + 257
+    pts, offs, _ = batch([n], ld_b=None, seed=11)
+    want_offs = check_case(pts, offs)
+    assert want_offs[-1] > keep_mask(pts[:256 * 2048], [0, 256 * 2048]).sum() > 0, "rows are kept in both scan tiles"
 
 
 @pytest.mark.parametrize("sizes", [(100, 200), (300, 0, 41), (257, 1, 600), (0, 513, 0), (0, 0), (256, 256, 1)], ids=lambda s: "-".join(map(str, s)))
