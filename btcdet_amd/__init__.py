@@ -15,12 +15,13 @@ Voxelizer, occupancy/occlusion target generator, sparse-3D-conv rulebook + fused
 * ``btcdet_amd.anchor_targets`` -- ``DeviceTargetAssigner`` / ``decode_boxes``: the anchor head's targets and boxes in four launches (opt-in)
 * ``btcdet_amd.anchor_loss``    -- ``anchor_loss``: the anchor head's loss, one launch forward and one backward (opt-in)
 * ``btcdet_amd.roi_targets_device`` -- ``DeviceProposalTargets``: the ROI head's targets (matching, sampling, canonical transform) in one launch (opt-in)
+* ``btcdet_amd.roi_loss``       -- ``roi_loss``: the ROI head's loss, one launch forward and one backward (opt-in)
 * ``btcdet_amd.occ_targets``    -- ``OccTargets3D`` (occupancy / occlusion grid generator)
 * ``btcdet_amd.vfe`` / ``backbones_3d`` / ``occ_head`` / ``pass_occ_vox`` / ``height_compression``
 
 All compute goes through ``libbtcdet_hip.so`` (hand-written HIP, C ABI in ``include/btcdet_hip.h``, ``btcdet_hip_infer.h``,
 ``btcdet_hip_augment.h``, ``btcdet_hip_bestmatch.h``, ``btcdet_hip_frames.h``, ``btcdet_hip_gtdb.h``, ``btcdet_hip_templates.h``,
-``btcdet_hip_infos.h``, ``btcdet_hip_heads.h``, ``btcdet_hip_anchor_loss.h``, ``btcdet_hip_roi_targets.h``).
+``btcdet_hip_infos.h``, ``btcdet_hip_heads.h``, ``btcdet_hip_anchor_loss.h``, ``btcdet_hip_roi_targets.h``, ``btcdet_hip_roi_loss.h``).
 """
 __version__ = "0.1.0"
 

@@ -1,6 +1,6 @@
 """ctypes binding of libbtcdet_hip.so (C ABI in include/btcdet_hip.h, include/btcdet_hip_infer.h, include/btcdet_hip_augment.h,
 include/btcdet_hip_bestmatch.h, include/btcdet_hip_frames.h, include/btcdet_hip_gtdb.h, include/btcdet_hip_templates.h,
-include/btcdet_hip_infos.h, include/btcdet_hip_heads.h, include/btcdet_hip_anchor_loss.h and include/btcdet_hip_roi_targets.h).
+include/btcdet_hip_infos.h, include/btcdet_hip_heads.h, include/btcdet_hip_anchor_loss.h, include/btcdet_hip_roi_targets.h and include/btcdet_hip_roi_loss.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails this module raises.
 torch is used only to own device memory and to name the current HIP stream.
@@ -287,6 +287,15 @@ _ROI_TARGETS_SIGS = {
 
 ROI_TARGETS_EXPORTED_SYMBOLS = tuple(_ROI_TARGETS_SIGS.keys())
 
+# the entry points of the twelfth public header, include/btcdet_hip_roi_loss.h: the loss over what btc_roi_targets leaves on the device
+_ROI_LOSS_SIGS = {
+    "btc_roi_loss_ws_bytes": (sz, [ci]),
+    "btc_roi_loss_fwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, vp, vp, vp, sz, vp]),
+    "btc_roi_loss_bwd": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp]),
+}
+
+ROI_LOSS_EXPORTED_SYMBOLS = tuple(_ROI_LOSS_SIGS.keys())
+
 
 def lib():
     """Load the HIP library; raise loudly if it has not been built (no fallback)."""
@@ -299,7 +308,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_INFER_SIGS.items()) + list(_AUGMENT_SIGS.items()) + list(_BESTMATCH_SIGS.items()) +
                                   list(_FRAMES_SIGS.items()) + list(_GTDB_SIGS.items()) + list(_TEMPLATES_SIGS.items()) + list(_INFOS_SIGS.items()) + list(_HEADS_SIGS.items()) +
-                                  list(_ANCHOR_LOSS_SIGS.items()) + list(_ROI_TARGETS_SIGS.items())):
+                                  list(_ANCHOR_LOSS_SIGS.items()) + list(_ROI_TARGETS_SIGS.items()) + list(_ROI_LOSS_SIGS.items())):
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -348,6 +348,28 @@ class ConvHead(nn.Module):
         from .roi_targets import rcnn_cls_loss, rcnn_reg_loss
         tb_dict = {} if tb_dict is None else tb_dict
         ret, cfg = self.forward_ret_dict, self.model_cfg.LOSS_CONFIG
+        # LOSS_CONFIG.DEVICE (opt-in): the loss by csrc/roi_loss.hip (roi_loss.py), one launch each way, where the configuration is one it
+        # computes and the call's tensors are float32 / int64 on the GPU; otherwise, and without the key, the torch formulation below.
+        # rcnn_loss_reg carries the corner term on both routes (the reference logs it before adding the corner term: DESIGN.md)
+        if getattr(self, "device_loss", None) is None:
+            self.device_loss = False
+            if cfg.get("DEVICE", False):
+                from . import roi_loss
+                why = roi_loss.unsupported_reason(cfg, self.box_coder)
+                self.device_loss = why is None
+                if why is not None:
+                    import logging
+                    logging.getLogger(__name__).warning("ROI_HEAD.LOSS_CONFIG.DEVICE is set but %s: the torch route is used", why)
+        if self.device_loss:
+            from . import roi_loss
+            if roi_loss.usable(ret):
+                with_corner = bool(cfg.CORNER_LOSS_REGULARIZATION)
+                loss, parts = roi_loss.roi_loss(ret, cfg.LOSS_WEIGHTS, with_corner)
+                vals = _lazy_scalars(parts, 5)
+                tb_dict.update(rcnn_loss_cls=vals[0], rcnn_loss_reg=vals[3], rcnn_loss=vals[4])
+                if with_corner:
+                    tb_dict["rcnn_loss_corner"] = vals[2]
+                return loss, tb_dict
         loss_cls = rcnn_cls_loss(ret["rcnn_cls"], ret["rcnn_cls_labels"], cfg)
         loss_reg, corner = rcnn_reg_loss(ret, self.box_coder, cfg)
         loss = loss_cls + loss_reg
